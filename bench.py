@@ -12,7 +12,14 @@ reported beside it as config.resident_window, never as `value`.  With N > 1 ever
 an independent window (BASELINE cfg5: weak scaling, no data-path collective) and the
 optimised keyframe poses are all-gathered over RCCL inside the timed region.
 
-    python bench.py --gpus 1 --steps 20 --warmup 3
+A plain run sets up, warms up, times the steps and prints the result line.  --full adds what
+takes runs of its own: the dominant kernel's roofline and the per-kernel times (HIP events),
+the resident / batched / covisibility-pattern / other-configuration / adapter figures and the
+CPU baselines with their parity spot-check.  --dump-outputs DIR writes what the last timed
+step handed its caller (poses, points, per-edge chi2 and outlier flags, the result counters)
+as DIR/<name>.npy; the inputs are seeded, so two builds can be compared output for output.
+
+    python bench.py --gpus 1 --steps 20 --warmup 3 [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 """
@@ -50,6 +57,43 @@ def measured_traffic(kernel_class):
     return None, None
 
 KERNEL_CLASSES = ["k_schur", "k_pcg", "k_point<backsub>", "k_decide", "setup(init+linearize+lambda)", "k_finalize"]
+
+DUMP_CAP_BYTES = 64 << 20
+
+
+def last_result(solver, rc):
+    """what solve_prepared() would have handed back for the handle's last solve_prepared(pack=False), which returned rc"""
+    import numpy as np
+    from movba import capi
+    d, keep, r, out = solver._prep
+    out = {k: np.array(v) for k, v in out.items()}
+    if rc != capi.OK:                                   # silent early return: nothing written, the inputs are the result
+        out["poses"][:] = keep["poses"]; out["points"][:] = keep["points"]
+    return solver._pack(r, out, rc)
+
+
+def result_arrays(r):
+    """the arrays a movba_lba_solve caller receives, copied out of the result buffers (pinned views that the next solve overwrites)"""
+    import numpy as np
+    counters = [r["status"], r["iters_done"], r["n_solves"], r["n_outliers"], r["cost0"], r["cost"]]
+    return {"poses": np.array(r["poses"]), "points": np.array(r["points"]), "chi2": np.array(r["chi2"]),
+            "outlier": np.array(r["outlier"]), "counters": np.array(counters, dtype=np.float64)}
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: one DIR/<name>.npy per array, float64 (float32 for flags).  Should the whole exceed 64 MB, every array is
+    cut to a fixed seeded sample of its rows, whose row numbers go to DIR/<name>_rows.npy."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {k: np.asarray(v, dtype=np.float32 if np.asarray(v).dtype.itemsize == 1 else np.float64) for k, v in arrays.items()}
+    total = sum(a.nbytes + 8 * a.shape[0] for a in arrays.values() if a.ndim)
+    keep = min(1.0, DUMP_CAP_BYTES / max(total, 1))
+    for name, a in arrays.items():
+        if keep < 1.0 and a.ndim and a.shape[0] > 1:
+            rows = np.sort(np.random.default_rng(0).choice(a.shape[0], max(1, int(a.shape[0] * keep)), replace=False))
+            a = a[rows]
+            np.save(os.path.join(dirname, name + "_rows.npy"), rows.astype(np.float64))
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(a))
 
 
 def algorithmic_bytes(K, F, P, E):
@@ -137,6 +181,13 @@ def main_windows(args):
     dt_max, solves_total = float(tt.item()), float(ss.item())
     if rank == 0 and os.environ.get("MOVBA_BENCH_DUMP_POSES"):
         np.save(os.environ["MOVBA_BENCH_DUMP_POSES"], gathered.detach().cpu().numpy())
+    if rank == 0 and args.dump_outputs:
+        # this rank's windows stacked (per-edge arrays end to end, window by window), and the poses of every rank's windows
+        per = [result_arrays(r) for r in res]
+        dump_outputs(args.dump_outputs, {"poses": np.stack([a["poses"] for a in per]), "points": np.stack([a["points"] for a in per]),
+                                         "chi2": np.concatenate([a["chi2"] for a in per]), "outlier": np.concatenate([a["outlier"] for a in per]),
+                                         "counters": np.stack([a["counters"] for a in per]),
+                                         "gathered_poses": gathered.detach().cpu().numpy()})
     if rank == 0:
         K, F, P = ws[0].n_free, ws[0].n_poses - ws[0].n_free, ws[0].n_points
         E_all = [w.n_edges for w in ws]
@@ -167,9 +218,13 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--config", default="cfg3", choices=["cfg2", "cfg3"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baselines")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
-    ap.add_argument("--no-extras", action="store_true", help="skip the informational extras (resident / batched / adapter runs): profiling passes")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: roofline and per-kernel times, the informational extras, the CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned to its caller as DIR/<name>.npy (float64; float32 for flags)")
+    ap.add_argument("--no-extras", action="store_true", help="(--full) skip the informational extras (resident / batched / adapter runs): profiling passes")
     ap.add_argument("--windows", type=int, default=0,
                     help="opt-in: BASELINE cfg5 as SURVEY 8(e) words it - ALWAYS this many windows (8: seeds 2000-2007), dealt round-robin "
                          "to the ranks and solved by each rank in one batched run (strong scaling); default 0 = one window per rank")
@@ -223,9 +278,11 @@ def main():
     solver.prepare(w, pinned=True)                       # descriptor + result buffers once, like a C++ caller's own (the adapter's:
                                                          # movba_host_alloc memory, which the solve's last kernel writes into directly)
 
+    last_rc = [None]
+
     def step():
         # host arrays in -> structure pass + H2D + whole LM loop on the device + D2H -> host arrays out
-        solver.solve_prepared(pack=False)
+        last_rc[0] = solver.solve_prepared(pack=False)
         if world > 1:
             return shard.gather_poses(pose_buf.cpu()) if rehearsal else shard.gather_poses(pose_buf)
         if rccl_world1:
@@ -240,27 +297,34 @@ def main():
 
     for _ in range(args.warmup):
         step()
-    # untimed pass with every kernel class bracketed by HIP events: find the dominant kernel
-    solver.set_profile_mask(0x3f); solver.reset_profile()
-    step(); torch.cuda.synchronize(dev)
-    prof_all = solver.profile()["kernels"]
-    dominant = max(KERNEL_CLASSES[:3], key=lambda k: prof_all[k]["ms"])
-    solver.set_profile_mask(1 << KERNEL_CLASSES.index(dominant)); solver.reset_profile()
+    if args.full:
+        # untimed pass with every kernel class bracketed by HIP events: find the dominant kernel
+        solver.set_profile_mask(0x3f); solver.reset_profile()
+        step(); torch.cuda.synchronize(dev)
+        prof_all = solver.profile()["kernels"]
+        dominant = max(KERNEL_CLASSES[:3], key=lambda k: prof_all[k]["ms"])
+        solver.set_profile_mask(1 << KERNEL_CLASSES.index(dominant))
+    solver.reset_profile()                               # host phases of the timed steps only
 
-    # HIP events bracket the dominant kernel's launches during the first tenth of the timed steps only (20 launches at the
-    # default 20 steps): an event pair per launch costs the solve ~2.5 us of GPU-side serialisation each - 5 % of a step that
-    # carries them (scripts/event_cost.py: 1.174 / 1.186 / 1.235 ms per step with events on 0 / 5 / 20 of 20 steps)
-    n_evt = max(1, args.steps // 10)
+    # (--full) HIP events bracket the dominant kernel's launches during the first tenth of the timed steps only (20 launches at
+    # the default 20 steps): an event pair per launch costs the solve ~2.5 us of GPU-side serialisation each - 5 % of a step
+    # that carries them (scripts/event_cost.py: 1.174 / 1.186 / 1.235 ms per step with events on 0 / 5 / 20 of 20 steps)
+    n_evt = max(1, args.steps // 10) if args.full else 0
     barrier()
     t0 = time.perf_counter()
     for i in range(args.steps):
-        if i == n_evt:
+        if args.full and i == n_evt:
             solver.set_profile_mask(0)
         gathered = step()
     barrier()
     dt = time.perf_counter() - t0
     prof = solver.profile()
-    res = solver.solve_prepared()                        # (untimed) the same solve once more, results unpacked
+    res = last_result(solver, last_rc[0])                # what the last timed step handed back, copied before anything runs again
+    if rank == 0 and args.dump_outputs:
+        outs = result_arrays(res)
+        if world > 1 or rccl_world1:
+            outs["gathered_poses"] = gathered.detach().cpu().numpy()
+        dump_outputs(args.dump_outputs, outs)
     solves_local = res["n_solves"] * args.steps         # the same window every step: bit-identical solves
 
     red_dev = torch.device("cpu") if rehearsal else dev
@@ -275,20 +339,6 @@ def main():
         # (tests: the gathered poses of the last timed step, one block per rank)
         np.save(os.environ["MOVBA_BENCH_DUMP_POSES"], gathered.detach().cpu().numpy())
     if rank == 0:
-        ab = algorithmic_bytes(K, F, P, E)
-        dk = prof["kernels"][dominant]
-        avg_s = dk["ms"] / max(dk["launches"], 1) * 1e-3
-        achieved = ab[dominant] / avg_s / 1e9 if avg_s > 0 else 0.0
-        chain_gbs = ab["B_iter"] * res["n_solves"] * args.steps / dt / 1e9
-        traffic, traffic_src = measured_traffic(dominant)
-        per_kernel = {}
-        for kc in KERNEL_CLASSES[:3]:
-            v = prof_all[kc]
-            a_s = v["ms"] / max(v["launches"], 1) * 1e-3
-            gbs = ab[kc] / a_s / 1e9 if a_s > 0 else 0.0
-            tr, _ = measured_traffic(kc)
-            per_kernel[kc] = {"avg_launch_us": a_s * 1e6, "algorithmic_bytes_per_launch": ab[kc], "achieved": gbs,
-                              "frac": gbs / HBM_PEAK_GBS, "traffic": tr}
         out = {
             "metric": "local-BA iterations/sec (50 KF x 20k MapPoint window)" if args.config == "cfg3"
                       else "local-BA iterations/sec (10 KF x 2k MapPoint window)",
@@ -304,23 +354,38 @@ def main():
                        "window_solves_per_s": world * args.steps / dt_max,
                        "parallelism": (f"{world} independent window(s), " + ("gloo pose all-gather, all ranks on ONE GPU (rehearsal)" if rehearsal else "RCCL pose all-gather")) if world > 1
                                       else ("1 window, RCCL pose all-gather over a one-rank nccl group (MOVBA_BENCH_RCCL_WORLD1)" if rccl_world1 else "1 window")},
-            "roofline": {"bound": "hbm", "kernel": dominant, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
-                         "algorithmic_bytes_per_launch": ab[dominant], "avg_launch_us": avg_s * 1e6,
-                         "launches_timed": dk["launches"],
-                         "launches_timed_note": f"HIP events around every launch of the dominant kernel during the first {n_evt} of the {args.steps} timed steps",
-
-                         "chain": {"B_iter_bytes": ab["B_iter"], "achieved": chain_gbs, "frac": chain_gbs / HBM_PEAK_GBS,
-                                   "note": "whole LM iteration (all kernels + launch gaps); latency-bound, not bandwidth-bound"},
-                         "per_kernel": per_kernel, "per_kernel_note": "HIP events around every launch of one untimed solve",
-                         "kernel_ms_per_step_all_classes": {k: v["ms"] for k, v in prof_all.items()}},
         }
-        out["per_kernel"] = per_kernel
+        if args.full:
+            ab = algorithmic_bytes(K, F, P, E)
+            dk = prof["kernels"][dominant]
+            avg_s = dk["ms"] / max(dk["launches"], 1) * 1e-3
+            achieved = ab[dominant] / avg_s / 1e9 if avg_s > 0 else 0.0
+            chain_gbs = ab["B_iter"] * res["n_solves"] * args.steps / dt / 1e9
+            traffic, traffic_src = measured_traffic(dominant)
+            per_kernel = {}
+            for kc in KERNEL_CLASSES[:3]:
+                v = prof_all[kc]
+                a_s = v["ms"] / max(v["launches"], 1) * 1e-3
+                gbs = ab[kc] / a_s / 1e9 if a_s > 0 else 0.0
+                tr, _ = measured_traffic(kc)
+                per_kernel[kc] = {"avg_launch_us": a_s * 1e6, "algorithmic_bytes_per_launch": ab[kc], "achieved": gbs,
+                                  "frac": gbs / HBM_PEAK_GBS, "traffic": tr}
+            out["roofline"] = {"bound": "hbm", "kernel": dominant, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                               "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
+                               "algorithmic_bytes_per_launch": ab[dominant], "avg_launch_us": avg_s * 1e6,
+                               "launches_timed": dk["launches"],
+                               "launches_timed_note": f"HIP events around every launch of the dominant kernel during the first {n_evt} of the {args.steps} timed steps",
+
+                               "chain": {"B_iter_bytes": ab["B_iter"], "achieved": chain_gbs, "frac": chain_gbs / HBM_PEAK_GBS,
+                                         "note": "whole LM iteration (all kernels + launch gaps); latency-bound, not bandwidth-bound"},
+                               "per_kernel": per_kernel, "per_kernel_note": "HIP events around every launch of one untimed solve",
+                               "kernel_ms_per_step_all_classes": {k: v["ms"] for k, v in prof_all.items()}}
+            out["per_kernel"] = per_kernel
         out["config"]["timed_region"] = ("movba_lba_solve: host arrays in -> structure pass, H2D, all launches, D2H -> results in "
                                          "host memory (SURVEY 8d; result arrays in movba_host_alloc memory, as the adapter's are); identical region "
                                          "for cpu_baseline")
         out["config"]["host_phase_ms_per_step"] = {k: prof[k] / args.steps for k in ("structure_ms", "upload_ms", "download_ms")}
-        extras = world == 1 and not args.no_extras
+        extras = args.full and world == 1 and not args.no_extras
         if extras:
             # for information only (never `value`): the LM loop alone with the window already resident in HBM
             # (movba_lba_upload once, then movba_lba_run per step)
@@ -507,7 +572,7 @@ def main():
                                                             "figure for an unpatched MapPoint (MapPoint::UpdateNormalAndDepth per point)"}
             except Exception as exc:                        # context only
                 out["config"]["adapter_host_ms"] = {"error": str(exc)}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             from oracle import oracle                       # CPU baseline leg: the oracle as the timed "port"
             oracle.build(force=True)                        # -march=native of THIS box's host cores
             cpu_model = "unknown"

@@ -22,7 +22,8 @@ def test_bench_with_two_ranks_gathers_the_poses_of_both_windows(built_lib, tmp_p
     dump = str(tmp_path / "poses.npy")
     env = dict(os.environ, MOVBA_BENCH_REHEARSAL="1", MASTER_ADDR="127.0.0.1", MOVBA_BENCH_DUMP_POSES=dump)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--no-cpu-baseline"]
+           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--full",
+           "--no-cpu-baseline"]
     p = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)     # a fresh child process, not an exec of this one
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
@@ -105,3 +106,29 @@ def test_bench_windows_mode_solves_the_eight_cfg5_windows_whatever_the_rank_coun
     finally:
         sv.close()
     assert abs(out["value"] - solves * 2 / (out["ms_per_step"] * 2e-3)) < 1e-6 * out["value"]
+
+
+def test_plain_bench_dumps_what_its_last_timed_step_returned(built_lib, tmp_path):
+    """bench.py --dump-outputs DIR on a plain run: the arrays of the last timed step are those of a solo solve of the same seeded
+    window (cfg3, seed 1003), the line holds the headline fields and none of the figures --full adds."""
+    out_dir = tmp_path / "outputs"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "1", "--dump-outputs", str(out_dir)]
+    p = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, p.stderr[-2000:]
+    lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    out = json.loads(lines[0])
+    assert out["steps"] == 4 and out["warmup"] == 1 and out["unit"] == "LM iterations/s" and out["dtype"] == "f64" and out["higher_is_better"]
+    assert not {"roofline", "per_kernel", "cpu_baseline", "cpu_baseline_all_cores"} & set(out)
+    assert not {"resident_window", "batched_windows", "covisibility_patterns", "other_baseline_configs", "adapter_host_ms"} & set(out["config"])
+    d = {n: np.load(out_dir / (n + ".npy")) for n in ("poses", "points", "chi2", "outlier", "counters")}
+    assert all(a.dtype == np.float64 for n, a in d.items() if n != "outlier") and d["outlier"].dtype == np.float32
+    sv = built_lib.Solver()
+    try:
+        r = sv.solve(synth.make_window(50, 10, 20000, 1003, run_lo=2, run_hi=10))
+    finally:
+        sv.close()
+    assert np.array_equal(d["poses"], r["poses"]) and np.array_equal(d["points"], r["points"]) and np.array_equal(d["chi2"], r["chi2"])
+    assert np.array_equal(d["outlier"], r["outlier"].astype(np.float32))
+    assert d["counters"][0] == r["status"] and d["counters"][2] == r["n_solves"] and d["counters"][3] == r["n_outliers"]
+    assert abs(out["value"] - r["n_solves"] * 4 / (out["ms_per_step"] * 4e-3)) < 1e-6 * out["value"]
