@@ -203,8 +203,16 @@ void fake_init(const DevWindow &w)
 {
     // reads everything the upload sent (the caller's arrays crossed on the copy stream: the solve waits for their event)
     g_sink += sum_bytes(w.pose0, 56 * (size_t)w.NP) + sum_bytes(w.point0, 24 * (size_t)w.P) + sum_bytes(w.obs, 16 * (size_t)w.E) + sum_bytes(w.isig, 8 * (size_t)w.E) +
-              sum_bytes(w.g_pose, 4 * (size_t)w.E) + sum_bytes(w.g_point, 4 * (size_t)w.E) + sum_bytes(w.slot, 4 * (size_t)w.E) + sum_bytes(w.items, sizeof(Item) * (size_t)w.nitems) +
-              sum_bytes(w.sched, 32) + sum_bytes(w.row_ptr, 4 * ((size_t)w.nfree + 1)) + sum_bytes(w.hidx, 4 * (size_t)w.NP);
+              sum_bytes(w.g_pose, 4 * (size_t)w.E) + sum_bytes(w.g_point, 4 * (size_t)w.E) + sum_bytes(w.slot, 4 * (size_t)w.E) + sum_bytes(w.hidx, 4 * (size_t)w.NP);
+    // the pair region where the view has one; the upload's early setup launches with its state view instead, which must hold
+    // none of it (k_init_pose and the first linearisation read none of it: a pair-region pointer there would be a stale one)
+    if (w.sched) g_sink += sum_bytes(w.items, sizeof(Item) * (size_t)w.nitems) + sum_bytes(w.sched, 32) + sum_bytes(w.row_ptr, 4 * ((size_t)w.nfree + 1));
+    else if (w.items || w.row_ptr || w.row_ent || w.pair_i || w.pair_j || w.pair_item_start || w.lane_plan || w.cblk_g || w.multi_pairs ||
+             w.part || w.blocks || w.blocks_c || w.blocks_ov || w.rec_d || w.img_b || w.dense.tiles || w.dense.pid || w.dense.flags ||
+             w.nitems || w.npairs || w.sched_per_xcd || w.direct_only || w.dense.G) {
+        std::fprintf(stderr, "fake device: a view without the pair region holds part of one\n");
+        std::abort();
+    }
     if (w.obs_r) g_sink += sum_bytes(w.obs_r, 8 * (size_t)w.E);
     if (w.dense.G > 0) g_sink += sum_bytes(w.dense.tasks, 32) + sum_bytes(w.dense.task_ptr, 4 * ((size_t)w.dense.G + 1));
     std::memcpy(w.st[0].pose, w.pose0, 56 * (size_t)w.NP);

@@ -966,11 +966,12 @@ def test_two_threads_two_handles_like_local_mapping_and_tracking(built_lib):
         a.close(); b.close()
 
 
-@pytest.mark.parametrize("case", ["stereo", "mono", "regrow", "ungrouped"])
+@pytest.mark.parametrize("case", ["stereo", "mono", "regrow", "ungrouped", "pinned"])
 def test_a_late_helper_thread_changes_nothing(built_lib, case):
     """The upload's helper thread (staging copies of the caller's arrays and their transfer) started 3 ms late: everything the
     calling thread takes from it must be behind a wait — a stereo window (layout depends on the stereo flag), an upload
-    that reallocates the arena, edges that are permuted after the helper's straight copies."""
+    that reallocates the arena, edges that are permuted after the helper's straight copies, and a window in the library's
+    pinned memory, whose early setup launches (slots, fill, first linearisation) the helper queues late."""
     s = built_lib.Solver(hooks=True)
     try:
         if case == "stereo":
@@ -987,7 +988,11 @@ def test_a_late_helper_thread_changes_nothing(built_lib, case):
         ref = ref_solver.solve(w)
         ref_solver.close()
         s.hook("helper_delay_us", 3000)
-        r = s.solve(w)
+        if case == "pinned":
+            s.prepare(w, pinned=True)
+            r = s.solve_prepared()
+        else:
+            r = s.solve(w)
         for k in ("poses", "points", "chi2", "outlier"):
             np.testing.assert_array_equal(r[k], ref[k])
     finally:
