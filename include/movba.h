@@ -302,6 +302,15 @@ typedef struct {
 } movba_pose_result;
 
 int  movba_pose_opt(movba_handle *h, const movba_pose_desc *desc, movba_pose_result *res);
+#define MOVBA_MAX_POSE_BATCH 1024
+/* movba_pose_opt on n frames at once (several Tracking sessions on one GPU): one set of launches, one synchronisation.
+ * Every frame's result equals, bit for bit, what movba_pose_opt returns for the same descriptor.  Every descriptor is
+ * checked first: one invalid descriptor (as movba_pose_opt rejects it), n < 0, n > MOVBA_MAX_POSE_BATCH or a NULL pointer
+ * gives MOVBA_ERR_ARG and nothing is solved.  n == 0: MOVBA_OK.  A frame with fewer than 4 matches gets status MOVBA_EMPTY
+ * and pose0, the others are still solved, and the call returns MOVBA_OK; results[i].status holds each frame's outcome.
+ * Uses the handle's staging buffer and pose scratch like movba_pose_opt (waits for an uploaded window's arrays first).
+ * Frames of more than ~3 000 matches (beyond what a workgroup keeps in LDS) go to a second launch. */
+int  movba_pose_opt_batch(movba_handle *h, const movba_pose_desc *descs, movba_pose_result *results, int32_t n);
 /* The minimal samples movba_pose_opt draws for (n matches, n_hyp, seed): n_hyp x 3 distinct match indices.  Host only. */
 int  movba_pose_ransac_samples(int32_t n, int32_t n_hyp, uint32_t seed, int32_t *out);
 

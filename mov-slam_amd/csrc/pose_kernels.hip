@@ -392,22 +392,40 @@ __device__ __forceinline__ void hyp_tables(const PoseDev &p, double *cand, doubl
 // The hypothesis stage over the whole chip: workgroup h solves sample h (one thread: a chain of dependent fp64 work) and
 // its four waves score the four candidates.  Inside k_pose_opt's single workgroup the scoring alone — 4 n_hyp candidates x n
 // matches x ~120 fp64 instructions on one CU — took 0.18 ms of a 0.42 ms call at 50 hypotheses and 500 matches.
-__global__ __launch_bounds__(kT) void k_pose_hyp(PoseDev p)
+// (One body for the solo grid and the batched one: both round alike, Makefile: -ffp-contract=on.)
+__device__ __forceinline__ void pose_hyp_body(const PoseDev &p, int h)
 {
     double *score; int *nsol;
     hyp_tables(p, p.cand, score, nsol);
-    const int h = blockIdx.x, tid = threadIdx.x;
+    const int tid = threadIdx.x;
     if (tid == 0) hyp_solve(p, p.Xw, p.obs, h, p.cand, nsol);
     __syncthreads();
     static_assert(kW == 4, "one wave per candidate of a sample");
     hyp_score(p, p.Xw, p.obs, p.isig, 4 * h + (tid >> 6), p.cand, nsol, score, tid & 63);
 }
 
+__global__ __launch_bounds__(kT) void k_pose_hyp(PoseDev p) { pose_hyp_body(p, blockIdx.x); }
+
+// movba_pose_opt_batch: one workgroup per (frame, sample) over every frame's samples; hyp_first[f] is the first workgroup of
+// frame f (prefix sum of n_hyp over the nf frames): a workgroup finds its frame by binary search, the largest f with
+// hyp_first[f] <= blockIdx.x (frames without samples own an empty range and are never found)
+__global__ __launch_bounds__(kT) void k_pose_hyp_b(const PoseDev *__restrict__ frames, const int32_t *__restrict__ hyp_first, int nf)
+{
+    const int b = blockIdx.x;
+    int lo = 0, hi = nf - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (hyp_first[mid] <= b) lo = mid; else hi = mid - 1;
+    }
+    pose_hyp_body(frames[lo], b - hyp_first[lo]);
+}
+
 // STAGED: the matches are read ONCE from where the host left them (its pinned staging buffer, across the bus) into LDS,
 // every pass of the 4 x 10 iterations then reads LDS, and the results are written straight back to the pinned buffer: no
 // copy engine on either side of the launch (small copies cost ~0.1 ms each, as much as the kernel itself).
+// The body of k_pose_opt (one frame, kernel argument) and k_pose_opt_b (frame blockIdx.x of a device array).
 template <bool STAGED>
-__global__ __launch_bounds__(kT) void k_pose_opt(PoseDev p)
+__device__ __forceinline__ void pose_opt_body(const PoseDev &p)
 {
     __shared__ __attribute__((aligned(16))) double lds[kRedLds];      // reduce_all: the waves' sums (two places), then a strip per wave
     int flip = 0;
@@ -752,12 +770,21 @@ __global__ __launch_bounds__(kT) void k_pose_opt(PoseDev p)
     }
 }
 
+template <bool STAGED>
+__global__ __launch_bounds__(kT) void k_pose_opt(PoseDev p) { pose_opt_body<STAGED>(p); }
+
+// movba_pose_opt_batch: workgroup f solves frame f (every frame's buffers are its own: pose_batch.cpp)
+template <bool STAGED>
+__global__ __launch_bounds__(kT) void k_pose_opt_b(const PoseDev *__restrict__ frames) { pose_opt_body<STAGED>(frames[blockIdx.x]); }
+
 size_t pose_ransac_bytes(int n_hyp) { return n_hyp > 0 ? (size_t)n_hyp * (48 + 8) * sizeof(double) + (size_t)n_hyp * sizeof(int) + 16 : 0; }
 size_t pose_opt_staged_lds_bytes(int n, int n_hyp) { return (size_t)n * 7 * sizeof(double) + (((size_t)n + 15) & ~(size_t)15) + pose_ransac_bytes(n_hyp); }
 
 hipError_t configure_pose_kernels()
 {
-    return hipFuncSetAttribute(reinterpret_cast<const void *>(k_pose_opt<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024);
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_pose_opt<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024);
+    if (e != hipSuccess) return e;
+    return hipFuncSetAttribute(reinterpret_cast<const void *>(k_pose_opt_b<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024);
 }
 
 hipError_t launch_pose_hyp(const PoseDev &p, hipStream_t s)
@@ -770,6 +797,20 @@ hipError_t launch_pose_opt(const PoseDev &p, bool staged, hipStream_t s)
 {
     if (staged) hipLaunchKernelGGL(k_pose_opt<true>, dim3(1), dim3(kT), pose_opt_staged_lds_bytes(p.n, p.hyp_done ? 0 : p.n_hyp), s, p);
     else hipLaunchKernelGGL(k_pose_opt<false>, dim3(1), dim3(kT), 0, s, p);
+    return hipGetLastError();
+}
+
+hipError_t launch_pose_hyp_batch(const PoseDev *frames, const int32_t *hyp_first, int n_frames, int n_blocks, hipStream_t s)
+{
+    if (n_frames > 0 && n_blocks > 0) hipLaunchKernelGGL(k_pose_hyp_b, dim3(n_blocks), dim3(kT), 0, s, frames, hyp_first, n_frames);
+    return hipGetLastError();
+}
+
+hipError_t launch_pose_opt_batch(const PoseDev *frames, int n_frames, bool staged, size_t lds_bytes, hipStream_t s)
+{
+    if (n_frames <= 0) return hipGetLastError();
+    if (staged) hipLaunchKernelGGL(k_pose_opt_b<true>, dim3(n_frames), dim3(kT), lds_bytes, s, frames);
+    else hipLaunchKernelGGL(k_pose_opt_b<false>, dim3(n_frames), dim3(kT), 0, s, frames);
     return hipGetLastError();
 }
 

@@ -90,7 +90,7 @@ EXPORTS = ["movba_version", "movba_status_string", "movba_create", "movba_destro
            "movba_lba_upload", "movba_lba_reset", "movba_lba_run", "movba_lba_download",
            "movba_lba_export_poses_device", "movba_lba_set_pose_export", "movba_get_profile", "movba_reset_profile",
            "movba_structure_probe", "movba_pose_opt", "movba_set_profile_mask", "movba_lba_run_batch", "movba_pose_ransac_samples",
-           "movba_host_alloc", "movba_host_free", "movba_dense_plan_probe"]
+           "movba_host_alloc", "movba_host_free", "movba_dense_plan_probe", "movba_pose_opt_batch"]
 
 _libs = {False: None, True: None}
 
@@ -141,6 +141,7 @@ def lib(hooks: bool = False):
         L.movba_set_profile_mask.argtypes = [C.c_void_p, C.c_int32]
         L.movba_structure_probe.argtypes = [C.POINTER(LbaDesc), C.POINTER(StructureInfo), _i, _i]
         L.movba_pose_opt.argtypes = [C.c_void_p, C.POINTER(PoseDesc), C.POINTER(PoseResult)]
+        L.movba_pose_opt_batch.argtypes = [C.c_void_p, C.POINTER(PoseDesc), C.POINTER(PoseResult), C.c_int32]
         L.movba_lba_run_batch.argtypes = [C.POINTER(C.c_void_p), C.c_int32]
         L.movba_pose_ransac_samples.argtypes = [C.c_int32, C.c_int32, C.c_uint32, _i]
         L.movba_host_alloc.argtypes = [C.c_size_t]
@@ -193,6 +194,31 @@ def make_desc(w, flags=FLAG_STALE_ERROR_QUIRK, stop=None, max_iters=None, max_tr
         assert keep["bf_kf"].shape == (d.n_poses,)
         d.bf_kf = _p(keep["bf_kf"], _d)
     return d, keep
+
+
+def _pose_desc(Xw, obs, pose0, cam, huber_delta, chi2_gate, rounds=4, its=10, inv_sigma2=None, ransac_iters=0, ransac_seed=1,
+               confidence=0.0, lo_iters=0):
+    """One frame -> (movba_pose_desc, movba_pose_result with its output arrays, the arrays both point into)."""
+    keep = dict(Xw=np.ascontiguousarray(Xw, np.float64), obs=np.ascontiguousarray(obs, np.float64))
+    n = len(keep["Xw"])
+    d = PoseDesc()
+    d.n = n; d.Xw = _p(keep["Xw"], _d); d.obs = _p(keep["obs"], _d)
+    if inv_sigma2 is not None:
+        keep["isg"] = np.ascontiguousarray(inv_sigma2, np.float64); d.inv_sigma2 = _p(keep["isg"], _d)
+    d.fx, d.fy, d.cx, d.cy = cam
+    d.pose0 = (C.c_double * 7)(*pose0)
+    d.huber_delta, d.chi2_gate, d.rounds, d.its_per_round = huber_delta, chi2_gate, rounds, its
+    d.ransac_iters, d.ransac_seed = ransac_iters, ransac_seed
+    d.confidence, d.lo_iters = confidence, lo_iters
+    keep["outlier"] = np.zeros(n, np.uint8); keep["chi2"] = np.zeros(n)
+    r = PoseResult(); r.outlier = _p(keep["outlier"], _u); r.chi2 = _p(keep["chi2"], _d)
+    return d, r, keep
+
+
+def _pose_dict(r, keep, status):
+    return dict(status=status, n_inliers=r.n_inliers, pose=np.array(r.pose[:]), outlier=keep["outlier"], chi2=keep["chi2"],
+                ransac_inliers=r.ransac_inliers, ransac_pose=np.array(r.ransac_pose[:]), lm_iters=r.lm_iters,
+                ransac_samples_used=r.ransac_samples_used, lo_accepted=r.lo_accepted, lo_inliers=r.lo_inliers)
 
 
 def structure_probe(w):
@@ -432,23 +458,25 @@ class Solver:
 
     def pose_opt(self, Xw, obs, pose0, cam, huber_delta, chi2_gate, rounds=4, its=10, inv_sigma2=None, ransac_iters=0, ransac_seed=1,
                  confidence=0.0, lo_iters=0) -> dict:
-        Xw = np.ascontiguousarray(Xw, np.float64); obs = np.ascontiguousarray(obs, np.float64)
-        n = len(Xw)
-        d = PoseDesc()
-        d.n = n; d.Xw = _p(Xw, _d); d.obs = _p(obs, _d)
-        isg = None
-        if inv_sigma2 is not None:
-            isg = np.ascontiguousarray(inv_sigma2, np.float64); d.inv_sigma2 = _p(isg, _d)
-        d.fx, d.fy, d.cx, d.cy = cam
-        d.pose0 = (C.c_double * 7)(*pose0)
-        d.huber_delta, d.chi2_gate, d.rounds, d.its_per_round = huber_delta, chi2_gate, rounds, its
-        d.ransac_iters, d.ransac_seed = ransac_iters, ransac_seed
-        d.confidence, d.lo_iters = confidence, lo_iters
-        outl = np.zeros(n, np.uint8); chi2 = np.zeros(n)
-        r = PoseResult(); r.outlier = _p(outl, _u); r.chi2 = _p(chi2, _d)
+        d, r, keep = _pose_desc(Xw, obs, pose0, cam, huber_delta, chi2_gate, rounds, its, inv_sigma2, ransac_iters, ransac_seed,
+                                confidence, lo_iters)
         rc = self._L.movba_pose_opt(self._h, C.byref(d), C.byref(r))
         if rc < 0:
             raise MovbaError(f"movba_pose_opt: {status_string(rc)}")
-        return dict(status=rc, n_inliers=r.n_inliers, pose=np.array(r.pose[:]), outlier=outl, chi2=chi2,
-                    ransac_inliers=r.ransac_inliers, ransac_pose=np.array(r.ransac_pose[:]), lm_iters=r.lm_iters,
-                    ransac_samples_used=r.ransac_samples_used, lo_accepted=r.lo_accepted, lo_inliers=r.lo_inliers)
+        return _pose_dict(r, keep, rc)
+
+    def pose_opt_batch(self, frames) -> list:
+        """movba_pose_opt_batch: `frames` is a list of dicts with pose_opt's keyword arguments (Xw, obs, pose0, cam,
+        huber_delta, chi2_gate, optional rounds, its, inv_sigma2, ransac_iters, ransac_seed, confidence, lo_iters); one dict per
+        frame back, pose_opt's keys with the frame's own status (0, or 3 = MOVBA_EMPTY for fewer than 4 matches)."""
+        n = len(frames)
+        descs = (PoseDesc * max(n, 1))(); res = (PoseResult * max(n, 1))()
+        keeps = []
+        for k, f in enumerate(frames):
+            d, r, keep = _pose_desc(**f)
+            descs[k] = d; res[k] = r
+            keeps.append(keep)
+        rc = self._L.movba_pose_opt_batch(self._h, descs, res, n)
+        if rc < 0:
+            raise MovbaError(f"movba_pose_opt_batch: {status_string(rc)}")
+        return [_pose_dict(res[k], keeps[k], res[k].status) for k in range(n)]
