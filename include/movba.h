@@ -37,6 +37,7 @@ extern "C" {
 #define MOVBA_STOPPED         1   /* *stop was set before the solve (Optimizer.cc:749-751)   */
 #define MOVBA_NO_FIXED        2   /* no fixed keyframe vertex (Optimizer.cc:525-529)          */
 #define MOVBA_EMPTY           3   /* nothing to optimise (no edges / no free vertex)          */
+#define MOVBA_SINGULAR        4   /* the information matrix (plus damping) is not positive definite: nothing written */
 #define MOVBA_ERR_ARG        -1
 #define MOVBA_ERR_HIP        -2   /* HIP runtime failure (no device, OOM, launch error)       */
 #define MOVBA_ERR_STATE      -3   /* call order violated (run before upload, ...)             */
@@ -184,6 +185,29 @@ int  movba_lba_upload(movba_handle *h, const movba_lba_desc *desc);   /* host st
 int  movba_lba_reset(movba_handle *h);                                /* restore uploaded state on device */
 int  movba_lba_run(movba_handle *h);                                  /* LM loop on device; returns after stream sync */
 int  movba_lba_download(movba_handle *h, movba_lba_result *res);      /* D2H + caller edge order */
+
+/* Marginal covariances of the window's last movba_lba_run / movba_lba_solve (status MOVBA_OK only; also after
+ * movba_lba_run_batch), at the estimate movba_lba_download returns - what g2o's SparseOptimizer::computeMarginals, Ceres'
+ * Covariance and GTSAM's Marginals give.
+ *   pose_cov   n_poses x 36, caller order: the row-major 6 x 6 block of keyframe i over the left tangent [omega; upsilon] of Tcw,
+ *              the update VertexSE3Expmap::oplusImpl applies (T <- exp(delta) T)
+ *   point_cov  n_points x 9: the row-major 3 x 3 block of map point l, world coordinates
+ * Either may be NULL, not both.  Definition: H is the full normal matrix of the window at the returned estimate as g2o's
+ * buildSystem and the LM kernels build it - every edge, inliers and gated outliers alike, stereo edges with their third row,
+ * the camera of each edge's keyframe, information rho'(chi2) inv_sigma2 I (Huber; no kernel when huber_delta <= 0) - with
+ * `damping` added to every diagonal entry.  The pose block of free keyframe i is the (i, i) block of H^-1, i.e. of S^-1 with
+ * S = Hpp - Hpl Hll^-1 Hlp; the point block of l is D + D (sum over its free observers i, j of B_il^T Sigma_ij B_jl) D with
+ * D = (Hll_l + damping I)^-1, B_il the 6 x 3 Hpl block of edge (i, l) and Sigma_ij the (i, j) block of S^-1.  Fixed keyframes
+ * get zero blocks (they fix the gauge); free keyframes and map points without an edge are not in the system: NaN blocks.
+ * Every block is exactly symmetric, and two calls give the same bits.
+ * Monocular windows with fewer than two fixed keyframes leave the scale free: H is singular, and at damping = 0 the call
+ * returns MOVBA_SINGULAR or values dominated by rounding - damp such windows (e.g. 1e-3).
+ * Returns MOVBA_ERR_ARG (NULL handle, both outputs NULL, damping negative or not finite), MOVBA_ERR_STATE (no upload, no run
+ * since the upload / reset, or a run whose status was not MOVBA_OK), MOVBA_SINGULAR (a non-positive or non-finite pivot in the
+ * factorisation of S, or a map point whose Hll + damping I is not positive definite).  On any non-zero status nothing is
+ * written.  The window, its results and later runs are left exactly as they were.  (Not g2o's computeMarginals to the bit: that
+ * one reuses the damped Hessian from before the last update.) */
+int  movba_lba_marginals(movba_handle *h, double damping, double *pose_cov, double *point_cov);
 
 /* movba_lba_run on the resident windows of n handles at once (multi-session serving: several independent windows on one
  * GPU): every kernel of an LM trial is one launch over the concatenated windows, with per-window LM state, so each window

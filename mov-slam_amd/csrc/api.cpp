@@ -275,6 +275,7 @@ const char *movba_status_string(int s)
     case MOVBA_STOPPED: return "stopped before solve";
     case MOVBA_NO_FIXED: return "no fixed keyframe";
     case MOVBA_EMPTY: return "nothing to optimise";
+    case MOVBA_SINGULAR: return "information matrix not positive definite (singular)";
     case MOVBA_ERR_ARG: return "invalid argument";
     case MOVBA_ERR_HIP: return "HIP runtime error";
     case MOVBA_ERR_STATE: return "invalid call order";
@@ -350,6 +351,8 @@ void movba_destroy(movba_handle *h)
     for (hipEvent_t e : h->ev_pool) (void)hipEventDestroy(e);
     if (h->arena) (void)hipFree(h->arena);
     if (h->pose_arena) (void)hipFree(h->pose_arena);
+    if (h->marg) (void)hipFree(h->marg);
+    if (h->marg_host) (void)hipHostFree(h->marg_host);
     for (hipStream_t st : h->batch_streams) if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); }
     for (hipEvent_t e : h->batch_ev) if (e) (void)hipEventDestroy(e);
     for (auto &ring : h->batch_phase_ev) for (hipEvent_t e : ring) if (e) (void)hipEventDestroy(e);

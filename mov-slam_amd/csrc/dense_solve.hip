@@ -424,7 +424,9 @@ size_t dense_tiles_doubles(int nfree)
 
 int dense_ntile(int nfree) { return (6 * nfree + NB - 1) / NB; }
 
-hipError_t launch_dense_solve(const DevWindow &w, hipStream_t s)
+// the assembly and factorisation launches of the direct solve; movba_lba_marginals runs them alone and reads the factor
+// (marginals.hip)
+hipError_t launch_dense_factor(const DevWindow &w, hipStream_t s)
 {
     const int nt = w.dense.ntile;
     hipLaunchKernelGGL(k_dense_assemble, dim3((nt + 1) * (nt + 2) / 2), dim3(256), 0, s, w);
@@ -435,6 +437,14 @@ hipError_t launch_dense_solve(const DevWindow &w, hipStream_t s)
         if (j > 0) for (int cc = 1; cc < m; ++cc) grid += m - cc + 1;
         hipLaunchKernelGGL(k_chol_step, dim3(grid), dim3(kStepThreads), lds, s, w, j);
     }
+    return hipGetLastError();
+}
+
+hipError_t launch_dense_solve(const DevWindow &w, hipStream_t s)
+{
+    const int nt = w.dense.ntile;
+    const hipError_t e = launch_dense_factor(w, s);
+    if (e != hipSuccess) return e;
     const size_t lds_b = ((size_t)nt * NB + NB * LD + 21 * NB + 16 + NB) * sizeof(double);
     if (nt > kBackStepsFrom) {
         for (int I = nt - 1; I >= 0; --I) hipLaunchKernelGGL(k_back_step, dim3(I + 1), dim3(256), 0, s, w, I);

@@ -196,6 +196,13 @@ struct movba_handle {
     // pose-only scratch
     char *pose_arena = nullptr;
     size_t pose_cap = 0;
+    // movba_lba_marginals (marginals.cpp): device scratch (controller, factor inverses, W, sigma, outputs) and the pinned image of
+    // the outputs, both grown on demand; the uploaded window's fixed flags (fixed keyframes get zero blocks)
+    char *marg = nullptr;
+    size_t marg_cap = 0;
+    char *marg_host = nullptr;
+    size_t marg_host_cap = 0;
+    std::vector<uint8_t> pose_fixed;
     movba::Worker packer;               // helper thread of movba_lba_upload
     // profiling
     std::vector<movba::EventPair> ev_used;

@@ -63,6 +63,7 @@ hipError_t configure_band();
 // direct solver (dense_solve.hip): assemble + one launch per block column + back substitution / pose update
 hipError_t configure_dense_kernels();
 hipError_t launch_dense_solve(const DevWindow &w, hipStream_t s);
+hipError_t launch_dense_factor(const DevWindow &w, hipStream_t s);      // its assembly and factorisation only (marginals.hip)
 // ... and in one launch (dense_persist.hip) when the static schedule fits (dense_plan.h)
 hipError_t configure_dense_persist();
 bool dense_persist_supported(const DensePlan &p);

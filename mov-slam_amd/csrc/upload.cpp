@@ -1259,15 +1259,21 @@ extern "C" {
 int movba_lba_upload(movba_handle *h, const movba_lba_desc *d)
 {
     if (!h || !d) return MOVBA_ERR_ARG;
+    int rc;
     {
         Upload u(h, d);
-        const int rc = u.run(true);
-        if (rc != kRetryClassic) return rc;
+        rc = u.run(true);
     }
-    // (edges not grouped by point, a free keyframe without an edge, an arena that had to grow under the device's own tables:
-    //  once more with the grouping pass on this thread)
-    Upload u(h, d);
-    return u.run(false);
+    if (rc == kRetryClassic) {
+        // (edges not grouped by point, a free keyframe without an edge, an arena that had to grow under the device's own tables:
+        //  once more with the grouping pass on this thread)
+        Upload u(h, d);
+        rc = u.run(false);
+    }
+    // (movba_lba_marginals: fixed keyframes get zero blocks, free ones outside the system NaN - the hessian index alone does not
+    //  tell them apart)
+    if (rc == MOVBA_OK) h->pose_fixed.assign(d->pose_fixed, d->pose_fixed + (d->pose_fixed ? d->n_poses : 0));
+    return rc;
 }
 
 int movba_lba_reset(movba_handle *h)

@@ -20,6 +20,7 @@ HOOKS_LIB_PATH = os.path.join(os.path.dirname(_HERE), "libmovba_hooks.so")
 MAX_TRACE = 128
 NKERNELS = 6
 OK, STOPPED, NO_FIXED, EMPTY, ERR_ARG, ERR_HIP, ERR_STATE, ERR_DEVICE_WAIT, ERR_TOO_LARGE = 0, 1, 2, 3, -1, -2, -3, -4, -5
+SINGULAR = 4
 FLAG_STALE_ERROR_QUIRK = 1
 
 _d = C.POINTER(C.c_double)
@@ -90,7 +91,7 @@ EXPORTS = ["movba_version", "movba_status_string", "movba_create", "movba_destro
            "movba_lba_upload", "movba_lba_reset", "movba_lba_run", "movba_lba_download",
            "movba_lba_export_poses_device", "movba_lba_set_pose_export", "movba_get_profile", "movba_reset_profile",
            "movba_structure_probe", "movba_pose_opt", "movba_set_profile_mask", "movba_lba_run_batch", "movba_pose_ransac_samples",
-           "movba_host_alloc", "movba_host_free", "movba_dense_plan_probe", "movba_pose_opt_batch"]
+           "movba_host_alloc", "movba_host_free", "movba_dense_plan_probe", "movba_pose_opt_batch", "movba_lba_marginals"]
 
 _libs = {False: None, True: None}
 
@@ -143,6 +144,7 @@ def lib(hooks: bool = False):
         L.movba_pose_opt.argtypes = [C.c_void_p, C.POINTER(PoseDesc), C.POINTER(PoseResult)]
         L.movba_pose_opt_batch.argtypes = [C.c_void_p, C.POINTER(PoseDesc), C.POINTER(PoseResult), C.c_int32]
         L.movba_lba_run_batch.argtypes = [C.POINTER(C.c_void_p), C.c_int32]
+        L.movba_lba_marginals.argtypes = [C.c_void_p, C.c_double, _d, _d]
         L.movba_pose_ransac_samples.argtypes = [C.c_int32, C.c_int32, C.c_uint32, _i]
         L.movba_host_alloc.argtypes = [C.c_size_t]
         L.movba_host_alloc.restype = C.c_void_p
@@ -432,6 +434,23 @@ class Solver:
         if rc != OK:
             out["poses"][:] = keep["poses"]; out["points"][:] = keep["points"]
         return self._pack(r, out, rc)
+
+    def marginals(self, damping: float = 0.0, points: bool = True, pose_cov=None, point_cov=None) -> dict:
+        """movba_lba_marginals on the window of the last run: dict(status, pose_cov (NP, 6, 6), point_cov (P, 3, 3) or None).
+        status OK or SINGULAR (nothing written: the arrays come back as they were - NaN unless given); errors raise.
+        pose_cov / point_cov: C-contiguous float64 arrays of those shapes to write into (allocated when not given)."""
+        d, keep = self._keep
+        if pose_cov is None:
+            pose_cov = np.full((d.n_poses, 6, 6), np.nan)
+        if points and point_cov is None:
+            point_cov = np.full((d.n_points, 3, 3), np.nan)
+        for a, shape in ((pose_cov, (d.n_poses, 6, 6)), (point_cov if points else None, (d.n_points, 3, 3))):
+            if a is not None and (a.shape != shape or a.dtype != np.float64 or not a.flags.c_contiguous):
+                raise ValueError(f"marginals: output arrays must be C-contiguous float64 of shape {shape}")
+        rc = self._L.movba_lba_marginals(self._h, float(damping), _p(pose_cov, _d), _p(point_cov, _d) if points else None)
+        if rc < 0:
+            raise MovbaError(f"movba_lba_marginals: {status_string(rc)}")
+        return dict(status=rc, pose_cov=pose_cov, point_cov=point_cov if points else None)
 
     def export_poses_device(self, dst_ptr: int, nbytes: int):
         rc = self._L.movba_lba_export_poses_device(self._h, C.c_void_p(dst_ptr), nbytes)
