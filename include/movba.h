@@ -338,6 +338,81 @@ int  movba_pose_opt_batch(movba_handle *h, const movba_pose_desc *descs, movba_p
 /* The minimal samples movba_pose_opt draws for (n matches, n_hyp, seed): n_hyp x 3 distinct match indices.  Host only. */
 int  movba_pose_ransac_samples(int32_t n, int32_t n_hyp, uint32_t seed, int32_t *out);
 
+/* The numeric body of LocalMapping::CreateNewMapPoints (LocalMapping.cc:313-476) for many keyframe pairs at once: every
+ * match of every pair is triangulated (or un-projected from a stereo observation) and taken through the reference's gates
+ * in the reference's order.  Choosing the neighbours (the baseline test at :268-287 with ComputeSceneMedianDepth included:
+ * a neighbour the reference skips is simply not passed), matching (MOVMatcher::SearchForTriangulation, :292) and the MapPoint
+ * bookkeeping (:483-494) stay with the caller.  Pairs are independent: one call serves one keyframe against its 30
+ * neighbours, or the keyframes of many sessions. */
+typedef struct {
+    /* views */
+    int32_t n_views;
+    int32_t n_pairs;
+    const double  *poses;       /* n_views x 7: qx qy qz qw tx ty tz = Tcw, as movba_lba_desc::poses (KeyFrame::GetPose, :237, :294);
+                                   the quaternion is normalised before use                                                */
+    const double  *cam;         /* n_views x 4: fx fy cx cy (KeyFrame::fx .. cy, :244-247, :302-305)                      */
+    const double  *bf;          /* n_views or NULL (monocular): KeyFrame::mbf (:430, :456)                                */
+    const double  *b;           /* n_views or NULL (monocular): KeyFrame::mb (:346, :348)                                 */
+    /* pairs: view 1 = the current keyframe (mpCurrentKeyFrame), view 2 = the neighbour (pKF2, :265) */
+    const int32_t *pair_view;   /* n_pairs x 2: indices into the views                                                    */
+    const int32_t *pair_ptr;    /* n_pairs + 1: ascending prefix into the matches, pair_ptr[0] = 0 (vMatchedIndices, :289-310) */
+    /* matches: n_matches = pair_ptr[n_pairs], those of pair p are [pair_ptr[p], pair_ptr[p + 1]) */
+    const double  *obs1;        /* n_matches x 2: kp1.pt in view 1, pixels (:318-320)                                     */
+    const double  *obs2;        /* n_matches x 2: kp2.pt in view 2 (:326-328)                                             */
+    const double  *ur1;         /* n_matches or NULL: mvuRight[idx1] (:321); < 0 or NULL: monocular observation (:322)    */
+    const double  *ur2;         /* n_matches or NULL: mvuRight[idx2] (:330-331)                                           */
+    const double  *depth1;      /* n_matches (required with ur1): mvDepth[idx1] (:346, KeyFrame::UnprojectStereo)         */
+    const double  *depth2;      /* n_matches (required with ur2): mvDepth[idx2] (:348)                                    */
+    /* gates */
+    double reproj_gate;         /* bound of the SQUARED reprojection error: the reference's delta = 5 (LocalMapping.cc:28, :422) */
+    double far_threshold;       /* mThFarPoints (:477); <= 0: off (mbFarPoints false)                                     */
+} movba_tri_desc;
+
+/* code[m]: what happened to match m, in the order the reference tests it (each reject is one of its `continue`s) */
+#define MOVBA_TRI_DLT            1   /* accepted: null vector of the 4 x 4 DLT system (:363-377)                         */
+#define MOVBA_TRI_STEREO1        2   /* accepted: un-projected from view 1's stereo depth (:378-383)                     */
+#define MOVBA_TRI_STEREO2        3   /* accepted: un-projected from view 2's stereo depth (:384-389)                     */
+#define MOVBA_TRI_REJ_W0        16   /* homogeneous w == 0 (:369-372)                                                    */
+#define MOVBA_TRI_REJ_PARALLAX  17   /* a stereo observation, but neither stereo parallax below the other (:390-393)     */
+#define MOVBA_TRI_REJ_DEPTH     18   /* non-positive stereo depth: UnprojectStereo false (:395-396)                      */
+#define MOVBA_TRI_REJ_BEHIND1   19   /* z1 <= 0 (:399-403)                                                               */
+#define MOVBA_TRI_REJ_BEHIND2   20   /* z2 <= 0 (:405-409)                                                               */
+#define MOVBA_TRI_REJ_REPROJ1   21   /* squared reprojection error in view 1 > reproj_gate (mono :416-426, stereo :427-437) */
+#define MOVBA_TRI_REJ_REPROJ2   22   /* ... in view 2 (mono :443-452, stereo :453-463)                                   */
+#define MOVBA_TRI_REJ_ZERO_DIST 23   /* the point lies in a camera centre (:472-475)                                     */
+#define MOVBA_TRI_REJ_FAR       24   /* a distance >= far_threshold (:477-480)                                           */
+
+typedef struct {
+    double  *points;            /* n_matches x 3 out, world (x3D, :483): written for every match that reached a 3-D position
+                                   (accepted, or rejected from MOVBA_TRI_REJ_BEHIND1 on), NaN for the three rejects before it */
+    uint8_t *code;              /* n_matches out: MOVBA_TRI_*                                                             */
+    int32_t  n_accepted;        /* matches with an accepted code (the reference's cnt, :490)                              */
+    int32_t  status;
+} movba_tri_result;
+
+/* Restated exactly, quirks included:
+ *   - rays R1^T xn1, R2^T xn2 over the normalised coordinates ((u - cx) / fx, (v - cy) / fy, 1) and cosParallaxRays (:334-339);
+ *   - the stereo parallaxes as the `if / else if` at :345-348 leaves them: cos(2 atan2(b / 2, depth)) for view 1 when its
+ *     observation is stereo, for view 2 ONLY when view 1's is not; the other keeps cosParallaxRays + 1;
+ *   - no stereo observation: DLT rows x P[2] - P[0], y P[2] - P[1] of both views with P = [Rcw | tcw], null vector, division
+ *     by w (cv::triangulatePoints, :365-376); a stereo observation: the view with the smaller parallax cosine is un-projected
+ *     (:378-389), (u - cx) depth / fx, (v - cy) depth / fy, depth taken to the world;
+ *   - the stereo reprojection in view 2 subtracts VIEW 1's bf over z2 (:456), as the reference does;
+ *   - comparisons as written (z <= 0, error > gate, distance == 0, distance >= threshold): a NaN passes them as it does there.
+ * The reference computes in float32 around a double SVD; this call is fp64 from the boundary to the result (as the LBA,
+ * DESIGN.md section 6), so its decisions can differ from the reference's only for matches within float rounding of a gate.
+ * The null vector comes from a one-sided Jacobi iteration on the 4 x 4 system itself (not on its normal matrix), with a fixed
+ * maximum of sweeps: the result of a match depends on that match and its two views alone - not on the other matches, the
+ * order or number of pairs, or how a set of matches is split over calls - and two calls give the same bits.
+ * Returns MOVBA_ERR_ARG (NULL handle / descriptor / result, a negative count, a NULL array that the counts make necessary,
+ * pair_ptr not ascending or not starting at 0, a view index out of range, ur1 / ur2 without bf and b or without its depth
+ * array, reproj_gate not finite, far_threshold NaN), MOVBA_ERR_HIP as elsewhere; every argument is checked before anything
+ * is queued, and on a non-zero status nothing is written except `status`.  No matches: MOVBA_OK, n_accepted = 0, nothing else
+ * written.  One packed copy to the device, one kernel launch, one synchronisation; `points` and `code` that lie in
+ * movba_host_alloc memory are written by the kernel itself.  May share a handle with an uploaded or solved window (it waits
+ * for the window's arrays before reusing the staging buffer): the window, its results and later runs stay as they were. */
+int  movba_triangulate(movba_handle *h, const movba_tri_desc *desc, movba_tri_result *res);
+
 #ifdef __cplusplus
 }
 #endif

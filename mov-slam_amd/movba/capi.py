@@ -87,11 +87,28 @@ class PoseResult(C.Structure):
                 ("ransac_samples_used", C.c_int32), ("lo_accepted", C.c_int32), ("lo_inliers", C.c_int32), ("pad_q", C.c_int32)]
 
 
+class TriDesc(C.Structure):
+    _fields_ = [("n_views", C.c_int32), ("n_pairs", C.c_int32), ("poses", _d), ("cam", _d), ("bf", _d), ("b", _d),
+                ("pair_view", _i), ("pair_ptr", _i), ("obs1", _d), ("obs2", _d), ("ur1", _d), ("ur2", _d),
+                ("depth1", _d), ("depth2", _d), ("reproj_gate", C.c_double), ("far_threshold", C.c_double)]
+
+
+class TriResult(C.Structure):
+    _fields_ = [("points", _d), ("code", _u), ("n_accepted", C.c_int32), ("status", C.c_int32)]
+
+
+# movba_tri_result::code (MOVBA_TRI_*): accepted ...
+TRI_DLT, TRI_STEREO1, TRI_STEREO2 = 1, 2, 3
+# ... and rejected, in the order the reference tests
+(TRI_REJ_W0, TRI_REJ_PARALLAX, TRI_REJ_DEPTH, TRI_REJ_BEHIND1, TRI_REJ_BEHIND2, TRI_REJ_REPROJ1, TRI_REJ_REPROJ2,
+ TRI_REJ_ZERO_DIST, TRI_REJ_FAR) = range(16, 25)
+TRI_ACCEPTED = (TRI_DLT, TRI_STEREO1, TRI_STEREO2)
+
 EXPORTS = ["movba_version", "movba_status_string", "movba_create", "movba_destroy", "movba_lba_solve",
            "movba_lba_upload", "movba_lba_reset", "movba_lba_run", "movba_lba_download",
            "movba_lba_export_poses_device", "movba_lba_set_pose_export", "movba_get_profile", "movba_reset_profile",
            "movba_structure_probe", "movba_pose_opt", "movba_set_profile_mask", "movba_lba_run_batch", "movba_pose_ransac_samples",
-           "movba_host_alloc", "movba_host_free", "movba_dense_plan_probe", "movba_pose_opt_batch", "movba_lba_marginals"]
+           "movba_host_alloc", "movba_host_free", "movba_dense_plan_probe", "movba_pose_opt_batch", "movba_lba_marginals", "movba_triangulate"]
 
 _libs = {False: None, True: None}
 
@@ -145,6 +162,7 @@ def lib(hooks: bool = False):
         L.movba_pose_opt_batch.argtypes = [C.c_void_p, C.POINTER(PoseDesc), C.POINTER(PoseResult), C.c_int32]
         L.movba_lba_run_batch.argtypes = [C.POINTER(C.c_void_p), C.c_int32]
         L.movba_lba_marginals.argtypes = [C.c_void_p, C.c_double, _d, _d]
+        L.movba_triangulate.argtypes = [C.c_void_p, C.POINTER(TriDesc), C.POINTER(TriResult)]
         L.movba_pose_ransac_samples.argtypes = [C.c_int32, C.c_int32, C.c_uint32, _i]
         L.movba_host_alloc.argtypes = [C.c_size_t]
         L.movba_host_alloc.restype = C.c_void_p
@@ -221,6 +239,31 @@ def _pose_dict(r, keep, status):
     return dict(status=status, n_inliers=r.n_inliers, pose=np.array(r.pose[:]), outlier=keep["outlier"], chi2=keep["chi2"],
                 ransac_inliers=r.ransac_inliers, ransac_pose=np.array(r.ransac_pose[:]), lm_iters=r.lm_iters,
                 ransac_samples_used=r.ransac_samples_used, lo_accepted=r.lo_accepted, lo_inliers=r.lo_inliers)
+
+
+def tri_desc(views, pairs, matches, reproj_gate=5.0, far_threshold=0.0):
+    """views dict(poses (V, 7), cam (V, 4), optional bf, b (V,)), pairs dict(pair_view (P, 2), pair_ptr (P + 1,)), matches
+    dict(obs1, obs2 (M, 2), optional ur1, ur2, depth1, depth2 (M,)) -> (movba_tri_desc, the arrays it points into)."""
+    keep = {}
+    d = TriDesc()
+
+    def arr(src, key, dtype, ptr):
+        a = src.get(key)
+        if a is None:
+            return
+        keep[key] = np.ascontiguousarray(a, dtype)
+        setattr(d, key, _p(keep[key], ptr))
+
+    for key in ("poses", "cam", "bf", "b"):
+        arr(views, key, np.float64, _d)
+    for key in ("pair_view", "pair_ptr"):
+        arr(pairs, key, np.int32, _i)
+    for key in ("obs1", "obs2", "ur1", "ur2", "depth1", "depth2"):
+        arr(matches, key, np.float64, _d)
+    d.n_views = len(keep["poses"]) if "poses" in keep else 0
+    d.n_pairs = len(keep["pair_view"]) if "pair_view" in keep else 0
+    d.reproj_gate, d.far_threshold = reproj_gate, far_threshold
+    return d, keep
 
 
 def structure_probe(w):
@@ -499,3 +542,21 @@ class Solver:
         if rc < 0:
             raise MovbaError(f"movba_pose_opt_batch: {status_string(rc)}")
         return [_pose_dict(res[k], keeps[k], res[k].status) for k in range(n)]
+
+    def triangulate(self, views, pairs, matches, reproj_gate=5.0, far_threshold=0.0, pinned=False, points=None, code=None) -> dict:
+        """movba_triangulate (the numeric body of LocalMapping::CreateNewMapPoints): views dict(poses, cam, optional bf, b),
+        pairs dict(pair_view, pair_ptr), matches dict(obs1, obs2, optional ur1, ur2, depth1, depth2) ->
+        dict(points (M, 3), code (M,) uint8 TRI_*, n_accepted, status).  pinned: result arrays in movba_host_alloc memory
+        (written by the kernel itself; they live until close()); points / code: arrays to write into instead."""
+        d, keep = tri_desc(views, pairs, matches, reproj_gate, far_threshold)
+        n = int(keep["pair_ptr"][-1]) if "pair_ptr" in keep and len(keep["pair_ptr"]) else 0
+        if points is None:
+            points = self._pinned((n, 3)) if pinned else np.zeros((n, 3))
+        if code is None:
+            code = self._pinned((n,), np.uint8) if pinned else np.zeros(n, np.uint8)
+        r = TriResult()
+        r.points = _p(points, _d); r.code = _p(code, _u)
+        rc = self._L.movba_triangulate(self._h, C.byref(d), C.byref(r))
+        if rc < 0:
+            raise MovbaError(f"movba_triangulate: {status_string(rc)}")
+        return dict(points=points, code=code, n_accepted=r.n_accepted, status=rc)

@@ -383,3 +383,141 @@ def pattern_cfg(name: str, seed: int | None = None) -> Window:
     if name == "shuffled":
         return shuffle_ids(cfg("cfg3"), 3003 if seed is None else seed)
     raise KeyError(name)
+
+
+# ---------------------------------------------------------------------------------------------
+# Keyframe pairs with matches to triangulate: the operand of movba_triangulate, i.e. what the loop of
+# LocalMapping::CreateNewMapPoints sees (/root/reference/src/LocalMapping.cc:263-476) after neighbour selection and matching.
+# ---------------------------------------------------------------------------------------------
+TRI_KINDS = ("normal", "mismatch", "behind_both", "behind_view2", "far", "depth_zero", "depth_negative", "wide_rays", "w_zero")
+
+
+def make_triangulation(n_pairs: int, n_per_pair, seed: int, stereo: bool = False, stereo_frac: float = 1.0,
+                       mismatch_frac: float = 0.05, special_frac: float = 0.01, pix_sigma: float = 0.5, bf: float = 120.0,
+                       far_threshold: float = 40.0, noise: bool = True) -> dict:
+    """A current keyframe (view 0) and n_pairs neighbours (views 1 .. n_pairs; pair p = (0, p + 1)) at baselines of 0.2 - 1.5 m,
+    n_per_pair matches each (an int, or one size per pair; 0 gives an empty pair).  Map points are drawn in the current
+    keyframe's image at depths of 4 - 30 m and projected into the neighbour; 0.5 px noise on both observations; everything is
+    rounded to float32 and widened, as the reference's floats arrive at the boundary.  A share of the matches are gross
+    mismatches (the second observation anywhere in the image), and `special_frac` of them each are placed so that every
+    reachable reject occurs: behind both cameras, between the two cameras of a neighbour that lies ahead (behind view 2),
+    beyond far_threshold, and with stereo=True a stereo depth of zero / below zero and rays more than 90 degrees apart (a
+    stereo observation whose parallax test fails).  The first neighbour is a pure sideways translation of the (identity)
+    current keyframe; its first match observes the principal point in both: the DLT's null vector has w = 0 exactly.
+    stereo: `stereo_frac` of the observations of either view that are closer than 12 m carry mvuRight / mvDepth (u_r = u - bf / z + noise, depth =
+    bf / (u - u_r)), the others -1.  -> dict(views, pairs, matches, reproj_gate, far_threshold, truth (M, 3), kind (M,):
+    index into TRI_KINDS): views / pairs / matches are the arguments of capi.Solver.triangulate."""
+    rng = np.random.default_rng(seed)
+    sizes = np.full(n_pairs, n_per_pair, dtype=np.int64) if np.isscalar(n_per_pair) else np.asarray(n_per_pair, dtype=np.int64)
+    assert len(sizes) == n_pairs
+    NV = n_pairs + 1
+    # views: the current keyframe at the origin with identity rotation; neighbours to the side / ahead, small yaw
+    k = np.arange(NV, dtype=np.float64)
+    base = rng.uniform(0.2, 1.5, NV) * np.where(rng.random(NV) < 0.5, -1.0, 1.0)
+    ahead = np.where(k % 4 == 2, rng.uniform(0.8, 1.2, NV), rng.uniform(-0.1, 0.1, NV))       # every fourth neighbour lies ahead
+    centres = np.stack([base, rng.uniform(-0.1, 0.1, NV), ahead], axis=1)
+    yaw = rng.uniform(-0.05, 0.05, NV)
+    centres[0] = 0.0; yaw[0] = 0.0
+    if NV > 1:
+        centres[1] = (0.5, 0.0, 0.0); yaw[1] = 0.0
+    Rcw, tcw = _poses_from(centres, yaw)
+    poses = np.zeros((NV, 7))
+    for i in range(NV):
+        poses[i, :4] = quat_from_R(Rcw[i]); poses[i, 4:] = tcw[i]
+    poses = _f32(poses)
+    poses[:, :4] /= np.linalg.norm(poses[:, :4], axis=1, keepdims=True)
+    Rcw = np.stack([R_from_quat(q) for q in poses[:, :4]]); tcw = poses[:, 4:].copy()      # (the geometry the observations see)
+    cam = np.tile(np.array([FX, FY, CX, CY]), (NV, 1))
+    b = bf / FX
+
+    pair_view = np.stack([np.zeros(n_pairs, np.int32), np.arange(1, NV, dtype=np.int32)], axis=1) if n_pairs else np.zeros((0, 2), np.int32)
+    pair_ptr = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32)
+    M = int(pair_ptr[-1])
+    v2 = np.repeat(pair_view[:, 1], sizes) if M else np.zeros(0, np.int32)
+    first_of_pair = np.zeros(M, bool)
+    first_of_pair[pair_ptr[:-1][sizes > 0]] = True
+
+    # kinds
+    kind = np.zeros(M, np.int64)
+    r = rng.random(M)
+    edges = mismatch_frac + special_frac * np.arange(0, 8)
+    kind[r < edges[0]] = 1
+    for j, name in enumerate(("behind_both", "behind_view2", "far") + (("depth_zero", "depth_negative", "wide_rays") if stereo else ())):
+        kind[(r >= edges[j]) & (r < edges[j + 1])] = TRI_KINDS.index(name)
+    ahead_of = centres[v2, 2] > 0.5 if M else np.zeros(0, bool)
+    kind[(kind == TRI_KINDS.index("behind_view2")) & ~ahead_of] = 0
+    if M and NV > 1 and sizes[0] > 0:
+        kind[0] = TRI_KINDS.index("w_zero")
+
+    u = rng.uniform(0.0, WIDTH, M); v = rng.uniform(0.0, HEIGHT, M)
+    depth = rng.uniform(4.0, 30.0, M)
+    depth = np.where(kind == TRI_KINDS.index("far"), rng.uniform(60.0, 100.0, M), depth)
+    depth = np.where(kind == TRI_KINDS.index("behind_both"), -depth, depth)
+    depth = np.where(kind == TRI_KINDS.index("behind_view2"), rng.uniform(0.3, 0.6, M), depth)
+    Xc1 = np.stack([(u - CX) / FX * depth, (v - CY) / FY * depth, depth], axis=1)
+    Xw = np.einsum('ji,mj->mi', Rcw[0], Xc1 - tcw[0])
+    Xc2 = np.einsum('mij,mj->mi', Rcw[v2], Xw) + tcw[v2]
+    z2 = Xc2[:, 2]
+    z2s = np.where(np.abs(z2) > 1e-9, z2, 1e-9)
+    obs1 = np.stack([u, v], axis=1)
+    obs2 = np.stack([FX * Xc2[:, 0] / z2s + CX, FY * Xc2[:, 1] / z2s + CY], axis=1)
+    if noise:
+        obs1 = obs1 + rng.normal(0.0, pix_sigma, (M, 2)); obs2 = obs2 + rng.normal(0.0, pix_sigma, (M, 2))
+    mm = kind == 1
+    obs2[mm] = np.stack([rng.uniform(0.0, WIDTH, M), rng.uniform(0.0, HEIGHT, M)], axis=1)[mm]
+    wide = kind == TRI_KINDS.index("wide_rays")
+    obs1[wide, 0] = rng.uniform(-40.0, -10.0, M)[wide]; obs2[wide, 0] = rng.uniform(WIDTH + 10.0, WIDTH + 40.0, M)[wide]
+    wz = kind == TRI_KINDS.index("w_zero")
+    obs1[wz] = (CX, CY); obs2[wz] = (CX, CY)
+
+    matches = dict(obs1=_f32(obs1), obs2=_f32(obs2))
+    views = dict(poses=poses, cam=cam)
+    if stereo:
+        def right(obs_u, z, is_view1):
+            zs = np.where(z > 0.1, z, 1.0)
+            ur = obs_u - bf / zs + (rng.normal(0.0, pix_sigma, M) if noise else 0.0)
+            st = (rng.random(M) < stereo_frac) & (z > 0.1) & (z < 12.0) & (ur >= 0.0) & ~wz     # (close points only, as ThDepth has it)
+            if not is_view1:
+                st &= ~wide                 # (rays wide apart, stereo in view 1 only: neither parallax test holds)
+            else:
+                st |= wide | (kind == TRI_KINDS.index("depth_zero")) | (kind == TRI_KINDS.index("depth_negative"))
+            ur = _f32(np.where(st, np.maximum(ur, 0.0), -1.0))
+            d = np.where(st, bf / np.maximum(obs_u - ur, 1e-3), -1.0)
+            return ur, d
+        ur1, d1 = right(matches["obs1"][:, 0], Xc1[:, 2], True)
+        ur2, d2 = right(matches["obs2"][:, 0], z2, False)
+        d1 = np.where(kind == TRI_KINDS.index("depth_zero"), 0.0, d1)
+        d1 = np.where(kind == TRI_KINDS.index("depth_negative"), -1.0, d1)
+        matches.update(ur1=ur1, ur2=ur2, depth1=_f32(d1), depth2=_f32(d2))
+        views.update(bf=_f32(np.full(NV, bf)), b=_f32(np.full(NV, b)))
+    return dict(views=views, pairs=dict(pair_view=pair_view, pair_ptr=pair_ptr), matches=matches, reproj_gate=5.0,
+                far_threshold=far_threshold, truth=Xw, kind=kind, meta=dict(seed=seed, n_pairs=n_pairs, M=M, stereo=stereo))
+
+
+def concat_triangulations(scenes) -> dict:
+    """Several make_triangulation scenes as ONE call's arguments (view indices shifted, pair_ptr continued): the keyframes of
+    several sessions at once.  Scenes without stereo arrays get monocular ones (-1) when any other has them."""
+    any_st = any("ur1" in s["matches"] for s in scenes)
+    poses, cam, bfs, bs, pv, sizes, truth, kind = [], [], [], [], [], [], [], []
+    m = {k: [] for k in ("obs1", "obs2", "ur1", "ur2", "depth1", "depth2")}
+    off = 0
+    for s in scenes:
+        nv = len(s["views"]["poses"]); n = int(s["pairs"]["pair_ptr"][-1])
+        poses.append(s["views"]["poses"]); cam.append(s["views"]["cam"])
+        bfs.append(s["views"].get("bf", np.zeros(nv))); bs.append(s["views"].get("b", np.zeros(nv)))
+        pv.append(s["pairs"]["pair_view"] + off); sizes.append(np.diff(s["pairs"]["pair_ptr"]))
+        off += nv
+        for k in ("obs1", "obs2"):
+            m[k].append(s["matches"][k])
+        for k in ("ur1", "ur2", "depth1", "depth2"):
+            m[k].append(s["matches"].get(k, np.full(n, -1.0)))
+        truth.append(s["truth"]); kind.append(s["kind"])
+    views = dict(poses=np.concatenate(poses), cam=np.concatenate(cam))
+    matches = dict(obs1=np.concatenate(m["obs1"]), obs2=np.concatenate(m["obs2"]))
+    if any_st:
+        views.update(bf=np.concatenate(bfs), b=np.concatenate(bs))
+        matches.update({k: np.concatenate(m[k]) for k in ("ur1", "ur2", "depth1", "depth2")})
+    pair_ptr = np.concatenate([[0], np.cumsum(np.concatenate(sizes))]).astype(np.int32)
+    return dict(views=views, pairs=dict(pair_view=np.concatenate(pv).astype(np.int32), pair_ptr=pair_ptr), matches=matches,
+                reproj_gate=scenes[0]["reproj_gate"], far_threshold=scenes[0]["far_threshold"], truth=np.concatenate(truth),
+                kind=np.concatenate(kind), meta=dict(M=int(pair_ptr[-1]), n_pairs=len(pair_ptr) - 1))
