@@ -413,6 +413,103 @@ typedef struct {
  * for the window's arrays before reusing the staging buffer): the window, its results and later runs stay as they were. */
 int  movba_triangulate(movba_handle *h, const movba_tri_desc *desc, movba_tri_result *res);
 
+/* Monocular map initialisation: the numeric body of TwoViewReconstruction::Reconstruct (TwoViewReconstruction.cc:68-118, called
+ * from Tracking.cc:620 through Pinhole::ReconstructWithTwoViews, Pinhole.cpp:90-100) for n independent frame pairs per call -
+ * cv::findEssentialMat(USAC_MAGSAC), cv::recoverPose and CheckRT.  One session's attempt is n = 1; a process that serves many
+ * sessions hands all of them to one set of launches. */
+typedef struct {
+    int32_t n_matches;          /* matches of the pair: the caller compacts vMatches12 >= 0 (TwoViewReconstruction.cc:54-63)     */
+    int32_t ransac_iters;       /* minimal samples scored, 1 .. MOVBA_MAX_TWO_VIEW_ITERS                                       */
+    const double *obs1;         /* n_matches x 2, pixels: mvKeys1[mvMatches12[i].first].pt (:81)                                */
+    const double *obs2;         /* n_matches x 2: mvKeys2[mvMatches12[i].second].pt (:82)                                       */
+    double fx, fy, cx, cy;      /* mK (:85-87)                                                                                  */
+    double threshold;           /* 1.0: findEssentialMat's threshold in pixels (:89)                                            */
+    double confidence;          /* 0.999 (:89); <= 0 or >= 1: every sample is eligible                                          */
+    double sigma;               /* 1.0: CheckRT's th2 = 4 sigma^2 (:110)                                                        */
+    double min_parallax_deg;    /* 1.0 (:41, :112)                                                                              */
+    double max_depth;           /* 50: cv::recoverPose's distance bound in the overload the reference calls (:94)               */
+    int32_t min_triangulated;   /* 50 (:65, :92)                                                                                */
+    uint32_t ransac_seed;
+} movba_two_view_desc;
+
+#define MOVBA_MAX_TWO_VIEW_ITERS 1024   /* (confidence 0.999 at half the matches wrong asks for 218 samples: MOVBA_MAX_RANSAC_ITERS is too few) */
+#define MOVBA_MAX_TWO_VIEW_BATCH 1024
+/* matches per pair at most: k_tv_check selects the parallax cosine by counting ranks, n^2 / 256 comparisons per thread of the
+ * pair's one workgroup (4 million at this bound, a few milliseconds); a frame holds a few thousand keypoints */
+#define MOVBA_MAX_TWO_VIEW_MATCHES 32768
+
+/* outcome: MOVBA_TV_OK, or the `return false` of Reconstruct that was taken */
+#define MOVBA_TV_OK            0
+#define MOVBA_TV_NO_MODEL      1   /* no candidate, or no match within the threshold: n == 0 (:91); also pairs under 5 matches */
+#define MOVBA_TV_FEW_GOOD      2   /* pass < minGood = max((int)(0.75 n), min_triangulated) (:92-99)                           */
+#define MOVBA_TV_LOW_PARALLAX  3   /* !(parallax > minParallax) (:112-117)                                                     */
+
+/* code[m]: what CheckRT did with match m (each reject is one of its `continue`s, in its order) */
+#define MOVBA_TV_CHK_NONE           0   /* CheckRT was not reached (MOVBA_TV_NO_MODEL)                                         */
+#define MOVBA_TV_CHK_GOOD           1   /* accepted (counted in nGood, point written) and vbGood: cosParallax < 0.99998 (:230) */
+#define MOVBA_TV_CHK_LOW_PARALLAX   2   /* accepted, but not vbGood                                                            */
+#define MOVBA_TV_CHK_REJ_NOT_INLIER 16  /* not in the mask after recoverPose (:163)                                            */
+#define MOVBA_TV_CHK_REJ_W0         17  /* homogeneous w == 0 (:179)                                                           */
+#define MOVBA_TV_CHK_REJ_BEHIND1    18  /* z1 <= 0 and cosParallax < 0.99998 (:195)                                            */
+#define MOVBA_TV_CHK_REJ_BEHIND2    19  /* z2 <= 0 and cosParallax < 0.99998 (:201)                                            */
+#define MOVBA_TV_CHK_REJ_REPROJ1    20  /* squared reprojection error in image 1 > th2 (:212)                                  */
+#define MOVBA_TV_CHK_REJ_REPROJ2    21  /* ... in image 2 (:223)                                                               */
+
+typedef struct {
+    double   pose[7];           /* T21: qx qy qz qw tx ty tz, |t| = 1 (:114); identity without a model                         */
+    double   E[9];              /* the winning essential matrix, row-major, Frobenius norm sqrt 2 (:89)                        */
+    double   parallax_deg;      /* CheckRT's parallax (:234-242)                                                               */
+    int32_t  outcome;           /* MOVBA_TV_*                                                                                  */
+    int32_t  status;            /* MOVBA_OK; MOVBA_EMPTY: fewer than 5 matches (outcome MOVBA_TV_NO_MODEL, no array written)   */
+    int32_t  n_inliers;         /* n = countNonZero(mask) after findEssentialMat (:90)                                         */
+    int32_t  n_pass;            /* recoverPose's return (:94)                                                                  */
+    int32_t  n_good;            /* CheckRT's return nGood (:244; the reference computes it and does not use it, :110)          */
+    int32_t  samples_used;      /* minimal samples the stopping rule admitted                                                  */
+    uint8_t *inlier;            /* n_matches out: the mask after recoverPose (:104-108)                                        */
+    double  *points;            /* n_matches x 3 out, camera-1 frame (vP3D, :227): NaN where CheckRT wrote none                */
+    uint8_t *good;              /* n_matches out: vbGood = vbTriangulated (:230-231)                                           */
+    uint8_t *code;              /* n_matches out: MOVBA_TV_CHK_*                                                               */
+    /* the hypothesis stage, each NULL or caller memory (what tests compare solver against solver) */
+    int32_t *hyp_nsol;          /* ransac_iters: candidates of every sample                                                    */
+    double  *hyp_E;             /* ransac_iters x 10 x 9: the candidates (zeros behind a sample's last)                        */
+    double  *hyp_loss;          /* ransac_iters x 10: their sigma-consensus++ loss over all matches (infinity behind the last) */
+} movba_two_view_result;
+
+/* OpenCV's own text is neither in the reference nor available to this project (as for cv::solvePnPRansac):
+ * stages 1 - 3 restate the PUBLISHED algorithms by the rules below and do not claim OpenCV's bits; stage 4 is the reference's
+ * own text and is restated exactly, quirks included.  fp64 from the boundary to the result.
+ *  1. Hypotheses.  Pixels are normalised with ONE focal length f = 0.5 (fx + fy) and (cx, cy): the reference hands
+ *     findEssentialMat and recoverPose that, not K (:85-89, :94); only CheckRT sees fx and fy apart.  Sample h = five distinct
+ *     matches (movba_two_view_samples).  Five-point relative pose (Nister 2004): null space of the 5 x 9 epipolar system, the ten
+ *     cubic constraints, elimination to a degree-10 polynomial in z, REAL roots only (derivative chain + bisection + Newton with
+ *     a fixed work bound on [-1, 1]; |z| > 1 through the reversed polynomial in 1 / z), back-substitution: up to 10 candidates.
+ *  2. Score.  Every candidate on all matches: squared Sampson distance in pixels, sigma-consensus++ loss (MAGSAC++, as
+ *     movba_pose_opt) with gate threshold^2.  Winner: lowest loss among the samples the stopping rule admits, N = log(1 -
+ *     confidence) / log(1 - w^5) with w the inlier ratio of the best candidate so far; ties go to the lower (sample, root) index.
+ *     inlier0[m] = Sampson^2 <= threshold^2, n_inliers = their number.  There is NO local optimisation / refit of the winner.
+ *  3. Pose recovery.  SVD of E (one-sided Jacobi), the four (R, t) with det R = +1; for each, every inlier0 match is triangulated
+ *     linearly over [I | 0], [R | t] in f-normalised coordinates and counted when 0 < z1 < max_depth and 0 < z2 < max_depth; the
+ *     largest count wins, ties in the order (R1, t), (R2, t), (R1, -t), (R2, -t).  n_pass = that count, inlier = inlier0 AND the test.
+ *  4. CheckRT (:120-245): P1 = K [I | 0], P2 = K [R | t] in pixels with the true fx, fy; DLT rows x P[2] - P[0], y P[2] - P[1];
+ *     w == 0 skips; cosParallax; the two depth tests that only reject when cosParallax < 0.99998; the two squared reprojection
+ *     errors against th2 = 4 sigma^2 with `>`; nGood, vbGood = cosParallax < 0.99998; the sorted cosines' element min(50, size - 1)
+ *     in degrees, 0 when nGood == 0; comparisons as written, so a NaN passes them as it does there.  (The reference computes
+ *     this stage in float32.)  CheckRT is also run when the outcome is MOVBA_TV_FEW_GOOD - the reference has returned by then -
+ *     so that a caller can see why an attempt failed; per-match arrays are written for every pair of 5 matches or more.
+ * Conventions as movba_pose_opt_batch and movba_triangulate: every descriptor is checked before anything is queued; a NULL
+ * pointer, n < 0, n > MOVBA_MAX_TWO_VIEW_BATCH or one invalid descriptor (n_matches negative or above MOVBA_MAX_TWO_VIEW_MATCHES; a NULL array that n_matches makes
+ * necessary; ransac_iters outside 1 .. MOVBA_MAX_TWO_VIEW_ITERS; fx, fy not positive and finite; any other parameter not finite;
+ * threshold or max_depth not positive; sigma or min_triangulated negative) gives MOVBA_ERR_ARG and nothing is written except
+ * `status`.  n == 0: MOVBA_OK.  A pair under 5 matches gets status MOVBA_EMPTY; the others are still solved and the call
+ * returns MOVBA_OK.  One packed copy to the device, three launches (k_tv_hyp, k_tv_recover, k_tv_check) over all pairs, one
+ * synchronisation; per-match arrays in movba_host_alloc memory are written by the kernels themselves.  A pair's result does
+ * not depend on the other pairs of the call or on their order, and two calls give the same bits.  May share a handle with an
+ * uploaded or solved window: the window, its results and later runs stay as they were. */
+int  movba_two_view(movba_handle *h, const movba_two_view_desc *descs, movba_two_view_result *results, int32_t n);
+/* The minimal samples movba_two_view draws for (n_matches >= 5, n_hyp, seed): n_hyp x 5 distinct match indices, from the
+ * generator of movba_pose_ransac_samples on another stream.  Host only. */
+int  movba_two_view_samples(int32_t n_matches, int32_t n_hyp, uint32_t seed, int32_t *out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,184 @@
+// movba_two_view (include/movba.h): monocular map initialisation for many frame pairs in one call.  The device pass is
+// two_view.hip (three kernels); this file checks every descriptor, packs pairs + matches + samples into the handle's staging
+// buffer, sends them with ONE copy, queues the launches and hands the results over after ONE synchronisation.  Per-match
+// result arrays that lie in movba_host_alloc memory are written by the kernels themselves; others arrive in the staging
+// buffer and are copied out.  The hypothesis tables (hyp_nsol / hyp_E / hyp_loss) stay in device scratch and are copied
+// only for a caller that asks for them.
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+#include "handle.h"
+#include "two_view.h"
+#include "two_view_math.h"
+
+using namespace movba;
+
+namespace {
+
+
+bool tv_desc_ok(const movba_two_view_desc &d, const movba_two_view_result &r)
+{
+    if (d.n_matches < 0 || d.n_matches > MOVBA_MAX_TWO_VIEW_MATCHES) return false;
+    if (d.ransac_iters < 1 || d.ransac_iters > MOVBA_MAX_TWO_VIEW_ITERS) return false;
+    if (!std::isfinite(d.fx) || !std::isfinite(d.fy) || !(d.fx > 0.0) || !(d.fy > 0.0)) return false;
+    if (!std::isfinite(d.cx) || !std::isfinite(d.cy)) return false;
+    if (!std::isfinite(d.threshold) || !(d.threshold > 0.0) || !std::isfinite(d.confidence)) return false;
+    if (!std::isfinite(d.sigma) || d.sigma < 0.0 || !std::isfinite(d.min_parallax_deg)) return false;
+    if (!std::isfinite(d.max_depth) || !(d.max_depth > 0.0) || d.min_triangulated < 0) return false;
+    if (d.n_matches > 0 && (!d.obs1 || !d.obs2)) return false;
+    if (d.n_matches >= 5 && (!r.inlier || !r.points || !r.good || !r.code)) return false;
+    return true;
+}
+
+}  // namespace
+
+extern "C" int movba_two_view_samples(int32_t n, int32_t n_hyp, uint32_t seed, int32_t *out)
+{
+    if (n < 5 || n_hyp < 0 || !out) return MOVBA_ERR_ARG;
+    // the xorshift32 generator of movba_pose_ransac_samples on another stream
+    uint32_t x = (seed ? seed : 0x9E3779B9u) ^ 0x85EBCA6Bu;
+    if (!x) x = 0x85EBCA6Bu;
+    auto next = [&]() { x ^= x << 13; x ^= x >> 17; x ^= x << 5; return x; };
+    for (int h = 0; h < n_hyp; ++h) {
+        int32_t *s = out + 5 * (size_t)h;
+        for (int k = 0; k < 5; ++k) {
+            bool again;
+            do {
+                s[k] = (int32_t)(next() % (uint32_t)n);
+                again = false;
+                for (int j = 0; j < k; ++j) again |= s[j] == s[k];
+            } while (again);
+        }
+    }
+    return MOVBA_OK;
+}
+
+extern "C" int movba_two_view(movba_handle *h, const movba_two_view_desc *descs, movba_two_view_result *results, int32_t n)
+{
+    if (!h || n < 0 || n > MOVBA_MAX_TWO_VIEW_BATCH) return MOVBA_ERR_ARG;
+    if (n == 0) return MOVBA_OK;
+    if (!descs || !results) return MOVBA_ERR_ARG;
+    for (int k = 0; k < n; ++k)
+        if (!tv_desc_ok(descs[k], results[k])) {
+            for (int j = 0; j < n; ++j) results[j].status = MOVBA_ERR_ARG;
+            return MOVBA_ERR_ARG;
+        }
+
+    // totals over the pairs that are solved (5 matches or more)
+    std::vector<TvPair> pairs((size_t)n);
+    std::vector<int32_t> hyp_first((size_t)n + 1, 0);
+    size_t M = 0, H = 0;
+    for (int k = 0; k < n; ++k) {
+        const movba_two_view_desc &d = descs[k];
+        TvPair &p = pairs[k];
+        std::memset(&p, 0, sizeof p);
+        const bool solve = d.n_matches >= 5;
+        p.n = solve ? d.n_matches : 0; p.n_hyp = solve ? d.ransac_iters : 0;
+        p.m0 = (int32_t)M; p.h0 = (int32_t)H;
+        p.min_tri = d.min_triangulated;
+        p.f = 0.5 * (d.fx + d.fy); p.fx = d.fx; p.fy = d.fy; p.cx = d.cx; p.cy = d.cy;
+        p.thr2 = d.threshold * d.threshold; p.conf = d.confidence; p.th2 = 4.0 * d.sigma * d.sigma;
+        p.min_par = d.min_parallax_deg; p.max_depth = d.max_depth;
+        hyp_first[k] = (int32_t)H;
+        M += (size_t)p.n; H += (size_t)p.n_hyp;
+    }
+    hyp_first[n] = (int32_t)H;
+    if (M > (size_t)1 << 28 || H > (size_t)1 << 22) {
+        for (int j = 0; j < n; ++j) results[j].status = MOVBA_ERR_ARG;
+        return MOVBA_ERR_ARG;
+    }
+    const size_t np = (size_t)n;
+
+    // Device arena: [0, h2d) the inputs (one H2D copy), then scratch.  Staging buffer: the same inputs, then the results that
+    // do not go straight into the caller's pinned arrays.
+    Carver c;
+    const size_t o_pairs = c.take<TvPair>(np), o_first = c.take<int32_t>(np + 1);
+    const size_t o_obs1 = c.take<double>(2 * M), o_obs2 = c.take<double>(2 * M), o_samp = c.take<int32_t>(5 * H);
+    const size_t h2d = c.off;
+    Carver dv = c;
+    const size_t o_cand = dv.take<double>(90 * H), o_loss = dv.take<double>(10 * H), o_cnt = dv.take<int32_t>(10 * H);
+    const size_t o_nsol = dv.take<int32_t>(H), o_inl0 = dv.take<uint8_t>(M), o_cos = dv.take<double>(M);
+    const size_t o_rec = dv.take<double>(kTvRecDoubles * np);
+    const size_t dev_total = dv.off;
+    const size_t o_out = c.take<double>(kTvOutDoubles * np);
+    const size_t o_inl = c.take<uint8_t>(M), o_pts = c.take<double>(3 * M), o_good = c.take<uint8_t>(M), o_code = c.take<uint8_t>(M);
+    const size_t total = c.off;
+
+    for (int j = 0; j < n; ++j) results[j].status = MOVBA_ERR_HIP;      // (until the device work is through)
+    HIP_TRY(hipSetDevice(h->device));
+    if (dev_total > h->pose_cap) {
+        if (h->pose_arena) { HIP_TRY(hipStreamSynchronize(h->stream)); HIP_TRY(hipFree(h->pose_arena)); h->pose_arena = nullptr; h->pose_cap = 0; }
+        const size_t cap = align_up(dev_total + dev_total / 4, 1 << 16);
+        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&h->pose_arena), cap));
+        h->pose_cap = cap;
+    }
+    int rc = ensure_stage(h, total); if (rc) return rc;
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    // (a window uploaded on this handle and not run yet: its arrays may still be crossing the bus out of the staging buffer)
+    HIP_TRY(hipEventSynchronize(h->copy_event));
+    h->export_in_run = false;        // (results a run may have left in the staging buffer are overwritten here: download exports again)
+
+    char *sg = h->stage, *ar = h->pose_arena;
+    struct View { unsigned long long *inl, *pts, *good, *code; };
+    std::vector<View> views(np);
+    for (int k = 0; k < n; ++k) {
+        const movba_two_view_desc &d = descs[k];
+        movba_two_view_result &r = results[k];
+        TvPair &p = pairs[k];
+        const size_t m = (size_t)p.n;
+        View &v = views[k];
+        v.inl = m ? host_block_view(r.inlier, m) : nullptr; v.pts = m ? host_block_view(r.points, sizeof(double) * 3 * m) : nullptr;
+        v.good = m ? host_block_view(r.good, m) : nullptr; v.code = m ? host_block_view(r.code, m) : nullptr;
+        p.inlier = v.inl ? reinterpret_cast<uint8_t *>(v.inl) : reinterpret_cast<uint8_t *>(h->stage_dev + o_inl) + p.m0;
+        p.points = v.pts ? reinterpret_cast<double *>(v.pts) : reinterpret_cast<double *>(h->stage_dev + o_pts) + 3 * (size_t)p.m0;
+        p.good = v.good ? reinterpret_cast<uint8_t *>(v.good) : reinterpret_cast<uint8_t *>(h->stage_dev + o_good) + p.m0;
+        p.code = v.code ? reinterpret_cast<uint8_t *>(v.code) : reinterpret_cast<uint8_t *>(h->stage_dev + o_code) + p.m0;
+        p.out = reinterpret_cast<double *>(h->stage_dev + o_out) + (size_t)kTvOutDoubles * k;
+        if (m) {
+            std::memcpy(sg + o_obs1 + sizeof(double) * 2 * (size_t)p.m0, d.obs1, sizeof(double) * 2 * m);
+            std::memcpy(sg + o_obs2 + sizeof(double) * 2 * (size_t)p.m0, d.obs2, sizeof(double) * 2 * m);
+            (void)movba_two_view_samples(p.n, p.n_hyp, d.ransac_seed, reinterpret_cast<int32_t *>(sg + o_samp) + 5 * (size_t)p.h0);
+        }
+    }
+    std::memcpy(sg + o_pairs, pairs.data(), sizeof(TvPair) * np);
+    std::memcpy(sg + o_first, hyp_first.data(), sizeof(int32_t) * (np + 1));
+
+    TvDev t{};
+    t.n_pairs = n; t.n_hyp_total = (int32_t)H;
+    t.pairs = reinterpret_cast<const TvPair *>(ar + o_pairs); t.hyp_first = reinterpret_cast<const int32_t *>(ar + o_first);
+    t.obs1 = reinterpret_cast<const double *>(ar + o_obs1); t.obs2 = reinterpret_cast<const double *>(ar + o_obs2);
+    t.samples = reinterpret_cast<const int32_t *>(ar + o_samp);
+    t.cand = reinterpret_cast<double *>(ar + o_cand); t.loss = reinterpret_cast<double *>(ar + o_loss);
+    t.cnt = reinterpret_cast<int32_t *>(ar + o_cnt); t.nsol = reinterpret_cast<int32_t *>(ar + o_nsol);
+    t.inl0 = reinterpret_cast<uint8_t *>(ar + o_inl0); t.cosv = reinterpret_cast<double *>(ar + o_cos);
+    t.rec = reinterpret_cast<double *>(ar + o_rec);
+
+    HIP_TRY(hipMemcpyAsync(ar, sg, h2d, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(launch_two_view(t, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+
+    for (int k = 0; k < n; ++k) {
+        movba_two_view_result &r = results[k];
+        const TvPair &p = pairs[k];
+        const size_t m = (size_t)p.n;
+        const View &v = views[k];
+        if (m && !v.inl) std::memcpy(r.inlier, sg + o_inl + p.m0, m);
+        if (m && !v.pts) std::memcpy(r.points, sg + o_pts + sizeof(double) * 3 * (size_t)p.m0, sizeof(double) * 3 * m);
+        if (m && !v.good) std::memcpy(r.good, sg + o_good + p.m0, m);
+        if (m && !v.code) std::memcpy(r.code, sg + o_code + p.m0, m);
+        const double *o = reinterpret_cast<const double *>(sg + o_out) + (size_t)kTvOutDoubles * k;
+        for (int e = 0; e < 7; ++e) r.pose[e] = o[e];
+        for (int e = 0; e < 9; ++e) r.E[e] = o[7 + e];
+        r.parallax_deg = o[16]; r.outcome = (int32_t)o[17]; r.n_inliers = (int32_t)o[18]; r.n_pass = (int32_t)o[19];
+        r.n_good = (int32_t)o[20]; r.samples_used = (int32_t)o[21];
+        if (m) {
+            const size_t nh = (size_t)p.n_hyp, h0 = (size_t)p.h0;
+            if (r.hyp_nsol) HIP_TRY(hipMemcpy(r.hyp_nsol, ar + o_nsol + sizeof(int32_t) * h0, sizeof(int32_t) * nh, hipMemcpyDeviceToHost));
+            if (r.hyp_E) HIP_TRY(hipMemcpy(r.hyp_E, ar + o_cand + sizeof(double) * 90 * h0, sizeof(double) * 90 * nh, hipMemcpyDeviceToHost));
+            if (r.hyp_loss) HIP_TRY(hipMemcpy(r.hyp_loss, ar + o_loss + sizeof(double) * 10 * h0, sizeof(double) * 10 * nh, hipMemcpyDeviceToHost));
+        }
+    }
+    for (int k = 0; k < n; ++k) results[k].status = pairs[k].n ? MOVBA_OK : MOVBA_EMPTY;
+    return MOVBA_OK;
+}

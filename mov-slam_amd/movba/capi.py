@@ -97,6 +97,30 @@ class TriResult(C.Structure):
     _fields_ = [("points", _d), ("code", _u), ("n_accepted", C.c_int32), ("status", C.c_int32)]
 
 
+class TwoViewDesc(C.Structure):
+    _fields_ = [("n_matches", C.c_int32), ("ransac_iters", C.c_int32), ("obs1", _d), ("obs2", _d),
+                ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double),
+                ("threshold", C.c_double), ("confidence", C.c_double), ("sigma", C.c_double), ("min_parallax_deg", C.c_double),
+                ("max_depth", C.c_double), ("min_triangulated", C.c_int32), ("ransac_seed", C.c_uint32)]
+
+
+class TwoViewResult(C.Structure):
+    _fields_ = [("pose", C.c_double * 7), ("E", C.c_double * 9), ("parallax_deg", C.c_double),
+                ("outcome", C.c_int32), ("status", C.c_int32), ("n_inliers", C.c_int32), ("n_pass", C.c_int32),
+                ("n_good", C.c_int32), ("samples_used", C.c_int32),
+                ("inlier", _u), ("points", _d), ("good", _u), ("code", _u),
+                ("hyp_nsol", _i), ("hyp_E", _d), ("hyp_loss", _d)]
+
+
+MAX_TWO_VIEW_ITERS = 1024
+MAX_TWO_VIEW_BATCH = 1024
+MAX_TWO_VIEW_MATCHES = 32768
+# movba_two_view_result::outcome (MOVBA_TV_*) and ::code (MOVBA_TV_CHK_*)
+TV_OK, TV_NO_MODEL, TV_FEW_GOOD, TV_LOW_PARALLAX = 0, 1, 2, 3
+TV_CHK_NONE, TV_CHK_GOOD, TV_CHK_LOW_PARALLAX = 0, 1, 2
+(TV_CHK_REJ_NOT_INLIER, TV_CHK_REJ_W0, TV_CHK_REJ_BEHIND1, TV_CHK_REJ_BEHIND2, TV_CHK_REJ_REPROJ1,
+ TV_CHK_REJ_REPROJ2) = range(16, 22)
+
 # movba_tri_result::code (MOVBA_TRI_*): accepted ...
 TRI_DLT, TRI_STEREO1, TRI_STEREO2 = 1, 2, 3
 # ... and rejected, in the order the reference tests
@@ -108,7 +132,8 @@ EXPORTS = ["movba_version", "movba_status_string", "movba_create", "movba_destro
            "movba_lba_upload", "movba_lba_reset", "movba_lba_run", "movba_lba_download",
            "movba_lba_export_poses_device", "movba_lba_set_pose_export", "movba_get_profile", "movba_reset_profile",
            "movba_structure_probe", "movba_pose_opt", "movba_set_profile_mask", "movba_lba_run_batch", "movba_pose_ransac_samples",
-           "movba_host_alloc", "movba_host_free", "movba_dense_plan_probe", "movba_pose_opt_batch", "movba_lba_marginals", "movba_triangulate"]
+           "movba_host_alloc", "movba_host_free", "movba_dense_plan_probe", "movba_pose_opt_batch", "movba_lba_marginals", "movba_triangulate",
+           "movba_two_view", "movba_two_view_samples"]
 
 _libs = {False: None, True: None}
 
@@ -164,6 +189,8 @@ def lib(hooks: bool = False):
         L.movba_lba_marginals.argtypes = [C.c_void_p, C.c_double, _d, _d]
         L.movba_triangulate.argtypes = [C.c_void_p, C.POINTER(TriDesc), C.POINTER(TriResult)]
         L.movba_pose_ransac_samples.argtypes = [C.c_int32, C.c_int32, C.c_uint32, _i]
+        L.movba_two_view.argtypes = [C.c_void_p, C.POINTER(TwoViewDesc), C.POINTER(TwoViewResult), C.c_int32]
+        L.movba_two_view_samples.argtypes = [C.c_int32, C.c_int32, C.c_uint32, _i]
         L.movba_host_alloc.argtypes = [C.c_size_t]
         L.movba_host_alloc.restype = C.c_void_p
         L.movba_dense_plan_probe.argtypes = [C.c_int32, C.c_int32, C.c_int32, _i, _i, C.c_int32, _i, C.c_int32]
@@ -299,6 +326,40 @@ def ransac_samples(n: int, n_hyp: int, seed: int) -> np.ndarray:
     if rc != OK:
         raise MovbaError(f"movba_pose_ransac_samples: {status_string(rc)}")
     return out
+
+
+def two_view_samples(n_matches: int, n_hyp: int, seed: int) -> np.ndarray:
+    """The minimal samples movba_two_view draws (host only): (n_hyp, 5) match indices."""
+    out = np.zeros((n_hyp, 5), np.int32)
+    rc = lib().movba_two_view_samples(n_matches, n_hyp, seed, _p(out, _i))
+    if rc != OK:
+        raise MovbaError(f"movba_two_view_samples: {status_string(rc)}")
+    return out
+
+
+TWO_VIEW_DEFAULTS = dict(threshold=1.0, confidence=0.999, sigma=1.0, min_parallax_deg=1.0, max_depth=50.0, min_triangulated=50,
+                         ransac_iters=256, ransac_seed=1)
+
+
+def two_view_desc(pair, alloc=np.zeros, diagnostics=False):
+    """One frame pair - dict(obs1, obs2 (M, 2), cam (fx, fy, cx, cy), optional TWO_VIEW_DEFAULTS keys) ->
+    (movba_two_view_desc, movba_two_view_result with its output arrays, the arrays both point into)."""
+    keep = dict(obs1=np.ascontiguousarray(pair["obs1"], np.float64).reshape(-1, 2),
+                obs2=np.ascontiguousarray(pair["obs2"], np.float64).reshape(-1, 2))
+    m = len(keep["obs1"])
+    d = TwoViewDesc()
+    d.n_matches = m; d.obs1 = _p(keep["obs1"], _d); d.obs2 = _p(keep["obs2"], _d)
+    d.fx, d.fy, d.cx, d.cy = pair["cam"]
+    for key, val in TWO_VIEW_DEFAULTS.items():
+        setattr(d, key, pair.get(key, val))
+    keep.update(inlier=alloc((m,), np.uint8), points=alloc((m, 3), np.float64), good=alloc((m,), np.uint8), code=alloc((m,), np.uint8))
+    r = TwoViewResult()
+    r.inlier = _p(keep["inlier"], _u); r.points = _p(keep["points"], _d); r.good = _p(keep["good"], _u); r.code = _p(keep["code"], _u)
+    if diagnostics:
+        nh = d.ransac_iters
+        keep.update(hyp_nsol=np.zeros(nh, np.int32), hyp_E=np.zeros((nh, 10, 3, 3)), hyp_loss=np.zeros((nh, 10)))
+        r.hyp_nsol = _p(keep["hyp_nsol"], _i); r.hyp_E = _p(keep["hyp_E"], _d); r.hyp_loss = _p(keep["hyp_loss"], _d)
+    return d, r, keep
 
 
 def run_batch(solvers) -> int:
@@ -560,3 +621,30 @@ class Solver:
         if rc < 0:
             raise MovbaError(f"movba_triangulate: {status_string(rc)}")
         return dict(points=points, code=code, n_accepted=r.n_accepted, status=rc)
+
+    def two_view(self, pairs, pinned=False, diagnostics=False) -> list:
+        """movba_two_view (monocular map initialisation, TwoViewReconstruction::Reconstruct) on a list of frame pairs:
+        dicts with obs1, obs2 (M, 2) pixels, cam (fx, fy, cx, cy) and optionally the keys of TWO_VIEW_DEFAULTS.  One dict per
+        pair back: status (0, or 3 = MOVBA_EMPTY under 5 matches), outcome (TV_*), pose (T21), E (3, 3), parallax_deg,
+        n_inliers, n_pass, n_good, samples_used, inlier, points, good, code (TV_CHK_*) per match and, with diagnostics,
+        hyp_nsol, hyp_E, hyp_loss.  pinned: per-match arrays in movba_host_alloc memory (written by the kernels; they live
+        until close())."""
+        n = len(pairs)
+        descs = (TwoViewDesc * max(n, 1))(); res = (TwoViewResult * max(n, 1))()
+        keeps = []
+        for k, pair in enumerate(pairs):
+            d, r, keep = two_view_desc(pair, self._pinned if pinned else np.zeros, diagnostics)
+            descs[k] = d; res[k] = r
+            keeps.append(keep)
+        rc = self._L.movba_two_view(self._h, descs, res, n)
+        if rc < 0:
+            raise MovbaError(f"movba_two_view: {status_string(rc)}")
+        out = []
+        for k in range(n):
+            r, keep = res[k], keeps[k]
+            o = dict(status=r.status, outcome=r.outcome, pose=np.array(r.pose[:]), E=np.array(r.E[:]).reshape(3, 3),
+                     parallax_deg=r.parallax_deg, n_inliers=r.n_inliers, n_pass=r.n_pass, n_good=r.n_good,
+                     samples_used=r.samples_used)
+            o.update({key: keep[key] for key in ("inlier", "points", "good", "code", "hyp_nsol", "hyp_E", "hyp_loss") if key in keep})
+            out.append(o)
+        return out

@@ -521,3 +521,51 @@ def concat_triangulations(scenes) -> dict:
     return dict(views=views, pairs=dict(pair_view=np.concatenate(pv).astype(np.int32), pair_ptr=pair_ptr), matches=matches,
                 reproj_gate=scenes[0]["reproj_gate"], far_threshold=scenes[0]["far_threshold"], truth=np.concatenate(truth),
                 kind=np.concatenate(kind), meta=dict(M=int(pair_ptr[-1]), n_pairs=len(pair_ptr) - 1))
+
+
+TWO_VIEW_SCENES = ("general", "planar", "rotation", "forward")
+
+
+def make_two_view(n_matches: int, inlier_frac: float = 0.7, noise_px: float = 0.5, seed: int = 0, scene: str = "general",
+                  cam=(458.0, 457.0, 367.0, 248.0), width: int = 752, height: int = 480) -> dict:
+    """One frame pair for movba_two_view: camera 1 at the origin, camera 2 at T21 = (R, t) with |t| = 1 (the unit the call
+    returns), points seen by both, noise_px of Gaussian noise on both observations; 1 - inlier_frac of the matches are gross
+    mismatches (the second observation anywhere in the image).  Scenes: `general` - depths of 4 - 40 baselines, sideways
+    motion with a few degrees of rotation; `planar` - every point on one slanted plane (the case an eight-point solver cannot
+    do); `rotation` - zero baseline (no parallax: initialisation must fail); `forward` - motion along the optical axis.
+    -> dict(obs1, obs2 (M, 2), cam, R (3, 3), t (3,): the true T21 (t = 0 for `rotation`), X (M, 3): the points in camera 1,
+    is_inlier (M,))."""
+    assert scene in TWO_VIEW_SCENES
+    rng = np.random.default_rng(seed)
+    fx, fy, cx, cy = cam
+    M = int(n_matches)
+    u = rng.uniform(20, width - 20, M); v = rng.uniform(20, height - 20, M)
+    if scene == "planar":
+        nrm = np.array([0.3, -0.2, -1.0]); nrm /= np.linalg.norm(nrm)
+        rays = np.stack([(u - cx) / fx, (v - cy) / fy, np.ones(M)], 1)
+        z = (nrm @ np.array([0.0, 0.0, 8.0])) / (rays @ nrm)            # the plane through (0, 0, 8)
+    else:
+        z = rng.uniform(4.0, 40.0, M)
+    X = np.stack([(u - cx) / fx * z, (v - cy) / fy * z, z], 1)
+    w = rng.uniform(-0.06, 0.06, 3)
+    if scene == "rotation":
+        w = rng.uniform(-0.1, 0.1, 3)
+    th = np.linalg.norm(w); k = w / th
+    K = np.array([[0, -k[2], k[1]], [k[2], 0, -k[0]], [-k[1], k[0], 0]])
+    R = np.eye(3) + np.sin(th) * K + (1 - np.cos(th)) * K @ K
+    if scene == "forward":
+        t = np.array([0.05, -0.03, -1.0])
+    else:
+        t = np.array([-1.0, rng.uniform(-0.2, 0.2), rng.uniform(-0.2, 0.2)])
+    t = t / np.linalg.norm(t)
+    if scene == "rotation":
+        t = np.zeros(3)
+    Y = X @ R.T + t
+    obs1 = np.stack([u, v], 1) + rng.normal(0, noise_px, (M, 2)) if noise_px > 0 else np.stack([u, v], 1)
+    obs2 = np.stack([fx * Y[:, 0] / Y[:, 2] + cx, fy * Y[:, 1] / Y[:, 2] + cy], 1)
+    if noise_px > 0:
+        obs2 = obs2 + rng.normal(0, noise_px, (M, 2))
+    is_inlier = rng.random(M) < inlier_frac
+    bad = ~is_inlier
+    obs2[bad] = np.stack([rng.uniform(0, width, bad.sum()), rng.uniform(0, height, bad.sum())], 1)
+    return dict(obs1=obs1, obs2=obs2, cam=tuple(float(c) for c in cam), R=R, t=t, X=X, is_inlier=is_inlier)
