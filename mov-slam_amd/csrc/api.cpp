@@ -136,6 +136,39 @@ int ensure_stage(movba_handle *h, size_t bytes)
     return MOVBA_OK;
 }
 
+int Scratch::grow(movba_handle *h, size_t bytes)
+{
+    if (bytes <= cap) return MOVBA_OK;
+    if (p) {
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        if (h->copy_stream) HIP_TRY(hipStreamSynchronize(h->copy_stream));
+        release();
+    }
+    const size_t c = align_up(bytes + bytes / 4, 1 << 20);
+    if (kind == Device) HIP_TRY(hipMalloc(reinterpret_cast<void **>(&p), c));
+    else HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&p), c, hipHostMallocDefault));
+    cap = c;
+    return MOVBA_OK;
+}
+
+void Scratch::release()
+{
+    if (p) (void)(kind == Device ? hipFree(p) : hipHostFree(p));
+    p = nullptr; cap = 0;
+}
+
+int begin_side_call(movba_handle *h, size_t dev_bytes, size_t stage_bytes)
+{
+    HIP_TRY(hipSetDevice(h->device));
+    if (dev_bytes) { const int rc = h->pose_scratch.grow(h, dev_bytes); if (rc) return rc; }
+    const int rc = ensure_stage(h, stage_bytes); if (rc) return rc;
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    // (a window uploaded on this handle and not run yet: its arrays may still be crossing the bus out of the staging buffer)
+    HIP_TRY(hipEventSynchronize(h->copy_event));
+    h->export_in_run = false;        // (results a run may have left in the staging buffer are overwritten here: download exports again)
+    return MOVBA_OK;
+}
+
 // device view of [p, p + bytes) if it lies inside a movba_host_alloc block, else nullptr
 unsigned long long *host_block_view(const void *p, size_t bytes)
 {
@@ -346,20 +379,13 @@ void movba_destroy(movba_handle *h)
     if (h->copy_stream) (void)hipStreamSynchronize(h->copy_stream);        // shared: stays
     if (h->copy_event) (void)hipEventDestroy(h->copy_event);
     if (h->edgeb_event) (void)hipEventDestroy(h->edgeb_event);
-    if (h->ingest_counter) (void)hipFree(h->ingest_counter);
     harvest_events(h);
     for (hipEvent_t e : h->ev_pool) (void)hipEventDestroy(e);
-    if (h->arena) (void)hipFree(h->arena);
-    if (h->pose_arena) (void)hipFree(h->pose_arena);
-    if (h->marg) (void)hipFree(h->marg);
-    if (h->marg_host) (void)hipHostFree(h->marg_host);
     for (hipStream_t st : h->batch_streams) if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); }
     for (hipEvent_t e : h->batch_ev) if (e) (void)hipEventDestroy(e);
     for (auto &ring : h->batch_phase_ev) for (hipEvent_t e : ring) if (e) (void)hipEventDestroy(e);
-    if (h->batch_dev) (void)hipFree(h->batch_dev);
-    if (h->batch_host) (void)hipHostFree(h->batch_host);
-    if (h->scratch) (void)hipFree(h->scratch);
-    if (h->scratch2) (void)hipFree(h->scratch2);
+    for (void *dev : { (void *)h->ingest_counter, (void *)h->arena }) if (dev) (void)hipFree(dev);
+    for (Scratch *b : { &h->scratch, &h->scratch2, &h->pose_scratch, &h->marg, &h->marg_host, &h->batch_dev, &h->batch_host }) b->release();
     if (h->stage) (void)hipHostFree(h->stage);
     if (h->hstat) (void)hipHostFree((void *)h->hstat);
     if (h->ctrl_host) (void)hipHostFree(h->ctrl_host);
@@ -767,18 +793,9 @@ int movba_lba_run_batch(movba_handle *const *hs, int32_t n)
             o_bp[g] = c.take<int32_t>(m + 1); o_bs[g] = c.take<int32_t>(m + 1); o_bf[g] = c.take<int32_t>(m + 1); o_bi[g] = c.take<int32_t>(m + 1);
             o_bw[g] = c.take<int32_t>(m + 1);
         }
-        if (c.off > h0->batch_cap) {
-            HIP_TRY(hipStreamSynchronize(s));
-            if (h0->batch_dev) { HIP_TRY(hipFree(h0->batch_dev)); h0->batch_dev = nullptr; }
-            if (h0->batch_host) { HIP_TRY(hipHostFree(h0->batch_host)); h0->batch_host = nullptr; }
-            h0->batch_cap = 0;
-            const size_t cap = align_up(2 * c.off, 1 << 16);
-            HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&h0->batch_host), cap, hipHostMallocDefault));
-            HIP_TRY(hipMalloc(reinterpret_cast<void **>(&h0->batch_dev), cap));
-            h0->batch_cap = cap;
-        }
+        { int rc = h0->batch_host.grow(h0, c.off); if (rc == MOVBA_OK) rc = h0->batch_dev.grow(h0, c.off); if (rc) return rc; }
         HIP_TRY(hipStreamSynchronize(s));           // the previous batch's H2D copy of this buffer has landed
-        char *bh = h0->batch_host, *bd = h0->batch_dev;
+        char *bh = h0->batch_host.p, *bd = h0->batch_dev.p;
         const int run_ahead = h0->opt.run_ahead;
         for (int g = 0; g < ngroups; ++g) {
             Group &G = grp[g];
@@ -1067,102 +1084,3 @@ int movba_reset_profile(movba_handle *h)
 }
 
 }  // extern "C"
-
-// ---------------------------------------------------------------------------------------
-// Optimizer::PoseOptimization (/root/reference/src/Optimizer.cc:397-459)
-// ---------------------------------------------------------------------------------------
-// minimal samples of the hypothesis stage: n_hyp triples of distinct match indices from a xorshift32 stream (the same
-// function feeds the oracle in the tests, so both sides score the same hypotheses)
-extern "C" int movba_pose_ransac_samples(int32_t n, int32_t n_hyp, uint32_t seed, int32_t *out)
-{
-    if (n < 3 || n_hyp < 0 || !out) return MOVBA_ERR_ARG;
-    uint32_t x = seed ? seed : 0x9E3779B9u;
-    auto next = [&]() { x ^= x << 13; x ^= x >> 17; x ^= x << 5; return x; };
-    for (int h = 0; h < n_hyp; ++h) {
-        int32_t a = (int32_t)(next() % (uint32_t)n), b, c;
-        do { b = (int32_t)(next() % (uint32_t)n); } while (b == a);
-        do { c = (int32_t)(next() % (uint32_t)n); } while (c == a || c == b);
-        out[3 * h] = a; out[3 * h + 1] = b; out[3 * h + 2] = c;
-    }
-    return MOVBA_OK;
-}
-
-extern "C" int movba_pose_opt(movba_handle *h, const movba_pose_desc *d, movba_pose_result *res)
-{
-    if (!h || !d || !res) return MOVBA_ERR_ARG;
-    res->status = MOVBA_ERR_ARG; res->n_inliers = 0; res->ransac_inliers = 0; res->lm_iters = 0;
-    res->ransac_samples_used = 0; res->lo_accepted = 0; res->lo_inliers = 0; res->pad_q = 0;
-    const int n = d->n;
-    const int n_hyp = d->ransac_iters > 0 ? std::min(d->ransac_iters, (int32_t)MOVBA_MAX_RANSAC_ITERS) : 0;
-    if (n < 0 || (n && (!d->Xw || !d->obs)) || d->rounds < 1 || d->its_per_round < 1) return MOVBA_ERR_ARG;
-    for (int k = 0; k < 7; ++k) res->pose[k] = d->pose0[k];
-    // fewer than 4 matches: the reference returns 0 without touching the frame (Optimizer.cc:415-418)
-    if (n < 4) { res->status = MOVBA_EMPTY; return MOVBA_EMPTY; }
-    HIP_TRY(hipSetDevice(h->device));
-    Carver c;
-    const size_t o_X = c.take<double>(3 * (size_t)n), o_obs = c.take<double>(2 * (size_t)n), o_is = c.take<double>(n);
-    const size_t o_samp = c.take<int32_t>(3 * (size_t)n_hyp + 1);
-    const size_t h2d = c.off;
-    const size_t o_chi = c.take<double>(n), o_pose = c.take<double>(24), o_lvl = c.take<uint8_t>(n);
-    const size_t d2h_end = c.off;
-    const size_t o_cand = c.take<uint8_t>(pose_ransac_bytes(n_hyp) + 16);
-    const size_t total = c.off;
-    // The hypothesis stage runs as a grid of its own over the whole chip (k_pose_hyp, one workgroup per sample) on a device
-    // copy of the matches; the LM kernel then only picks the best candidate.  The LM keeps the matches in LDS when they fit
-    // (staged), reading them once from the device copy (hypothesis stage on) or straight from the pinned buffer (off), and
-    // writes its results back into the pinned buffer itself.
-    const bool grid_hyp = n_hyp > 0;
-    const bool staged = pose_opt_staged_lds_bytes(n, 0) <= 144 * 1024;
-    const bool need_arena = !staged || grid_hyp;
-    if (need_arena && total > h->pose_cap) {
-        if (h->pose_arena) { HIP_TRY(hipStreamSynchronize(h->stream)); HIP_TRY(hipFree(h->pose_arena)); h->pose_arena = nullptr; h->pose_cap = 0; }
-        const size_t cap = align_up(2 * total, 1 << 16);
-        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&h->pose_arena), cap));
-        h->pose_cap = cap;
-    }
-    int rc = ensure_stage(h, total); if (rc) return rc;
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    // (a window uploaded on this handle and not run yet: its arrays may still be crossing the bus out of the staging buffer)
-    HIP_TRY(hipEventSynchronize(h->copy_event));
-    h->export_in_run = false;        // (results a run may have left in the staging buffer are overwritten here: download exports again)
-    char *sg = h->stage;
-    std::memcpy(sg + o_X, d->Xw, sizeof(double) * 3 * (size_t)n);
-    std::memcpy(sg + o_obs, d->obs, sizeof(double) * 2 * (size_t)n);
-    double *isg = reinterpret_cast<double *>(sg + o_is);
-    for (int i = 0; i < n; ++i) isg[i] = d->inv_sigma2 ? d->inv_sigma2[i] : 1.0;
-    if (n_hyp > 0) (void)movba_pose_ransac_samples(n, n_hyp, d->ransac_seed, reinterpret_cast<int32_t *>(sg + o_samp));
-    if (need_arena) HIP_TRY(hipMemcpyAsync(h->pose_arena, sg, h2d, hipMemcpyHostToDevice, h->stream));
-    PoseDev p{};
-    p.n = n; p.rounds = d->rounds; p.its = d->its_per_round; p.n_hyp = n_hyp; p.hyp_done = 0;
-    p.confidence = d->confidence; p.lo_its = n_hyp > 0 && d->lo_iters > 0 ? d->lo_iters : 0;
-    p.fx = d->fx; p.fy = d->fy; p.cx = d->cx; p.cy = d->cy; p.huber_delta = d->huber_delta; p.chi2_gate = d->chi2_gate;
-    for (int k = 0; k < 7; ++k) p.pose0[k] = d->pose0[k];
-    char *in = need_arena ? h->pose_arena : h->stage_dev;          // where the kernels read the matches
-    char *out = staged ? h->stage_dev : h->pose_arena;              // where the LM kernel leaves its results
-    p.Xw = reinterpret_cast<double *>(in + o_X); p.obs = reinterpret_cast<double *>(in + o_obs); p.isig = reinterpret_cast<double *>(in + o_is);
-    p.samples = reinterpret_cast<const int32_t *>(in + o_samp);
-    p.chi2 = reinterpret_cast<double *>(out + o_chi); p.pose_out = reinterpret_cast<double *>(out + o_pose); p.level1 = reinterpret_cast<uint8_t *>(out + o_lvl);
-    p.cand = need_arena ? reinterpret_cast<double *>(h->pose_arena + o_cand) : nullptr;
-    if (grid_hyp) {
-        HIP_TRY(launch_pose_hyp(p, h->stream));
-        p.hyp_done = 1;
-    }
-    HIP_TRY(launch_pose_opt(p, staged, h->stream));
-    if (!staged) HIP_TRY(hipMemcpyAsync(sg + o_chi, h->pose_arena + o_chi, d2h_end - o_chi, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    const double *po = reinterpret_cast<const double *>(sg + o_pose);
-    for (int k = 0; k < 7; ++k) res->pose[k] = po[k];
-    res->n_inliers = (int32_t)po[7];
-    res->ransac_inliers = n_hyp > 0 ? (int32_t)po[8] : 0;
-    res->lm_iters = (int32_t)po[16];
-#ifdef MOVBA_CLOCK_STAMP
-    std::fprintf(stderr, "libmovba[stamp]: k_pose_opt, cycles per LM iteration (%d): system pass %.0f, reduction of 28 %.0f, solve + update %.0f, cost pass + reduction %.0f\n",
-                 res->lm_iters, po[20] / res->lm_iters, po[21] / res->lm_iters, po[22] / res->lm_iters, po[23] / res->lm_iters);
-#endif
-    res->ransac_samples_used = n_hyp > 0 ? (int32_t)po[17] : 0; res->lo_accepted = n_hyp > 0 ? (int32_t)po[18] : 0; res->lo_inliers = n_hyp > 0 ? (int32_t)po[19] : 0;
-    for (int k = 0; k < 7; ++k) res->ransac_pose[k] = n_hyp > 0 ? po[9 + k] : d->pose0[k];
-    if (res->outlier) std::memcpy(res->outlier, sg + o_lvl, (size_t)n);
-    if (res->chi2) std::memcpy(res->chi2, sg + o_chi, sizeof(double) * (size_t)n);
-    res->status = MOVBA_OK;
-    return MOVBA_OK;
-}

@@ -117,9 +117,25 @@ struct Worker {
     MOVBA_INTERNAL ~Worker();
 };
 
+// A buffer of the handle that is grown on demand and never shrunk: device memory or pinned host memory (default flags).
+// One policy for all of them (api.cpp): a quarter more than asked for, rounded up to 1 MiB, and both of the handle's
+// streams drained before the old block is freed.  No destructor: movba_destroy releases them behind its own drains.
+struct Scratch {
+    enum Kind { Device, Pinned };
+    char *p = nullptr;
+    size_t cap = 0;
+    Kind kind = Device;
+    MOVBA_INTERNAL int grow(movba_handle *h, size_t bytes);
+    MOVBA_INTERNAL void release();
+};
+
 // arena / pinned staging buffer of a handle grown to `bytes` (never shrunk; both streams drained first)
 MOVBA_INTERNAL int ensure_arena(movba_handle *h, size_t bytes);
 MOVBA_INTERNAL int ensure_stage(movba_handle *h, size_t bytes);
+// The front of every call that borrows the staging buffer and the pose scratch beside the LBA calls (movba_pose_opt,
+// movba_pose_opt_batch, movba_triangulate, movba_two_view): the device is set, the pose scratch holds dev_bytes (0: the call
+// needs no device copy) and the staging buffer stage_bytes, and nothing of an earlier call or upload is still using either.
+MOVBA_INTERNAL int begin_side_call(movba_handle *h, size_t dev_bytes, size_t stage_bytes);
 // device view of [p, p + bytes) if it lies inside a movba_host_alloc block, else nullptr
 MOVBA_INTERNAL unsigned long long *host_block_view(const void *p, size_t bytes);
 
@@ -183,25 +199,17 @@ struct movba_handle {
     int dplan_nt = -1;
     bool dense_flags_clean = false;     // the window's hand-off flags have been zeroed since its upload (done before the first direct launch)
     unsigned dense_epoch = 0;           // direct launches on this window so far: the value a flag of the current launch carries
-    char *scratch = nullptr;            // structure-pass temporaries (struct_kernels.hip)
-    size_t scratch_cap = 0;
-    char *scratch2 = nullptr;           // ... of the sort-based fill (struct_sort.hip): keys, values, rocPRIM's temporary storage
-    size_t scratch2_cap = 0;
+    movba::Scratch scratch;             // structure-pass temporaries (struct_kernels.hip)
+    movba::Scratch scratch2;            // ... of the sort-based fill (struct_sort.hip): keys, values, rocPRIM's temporary storage
     // movba_lba_run_batch (kept by the first handle of a batch): device views, PCG plans and block prefixes of the windows
-    char *batch_host = nullptr, *batch_dev = nullptr;
-    size_t batch_cap = 0;
+    movba::Scratch batch_host{nullptr, 0, movba::Scratch::Pinned}, batch_dev;
     hipStream_t batch_streams[movba::kMaxGroups] = {};  // extra streams of a batched run (groups of windows run out of phase); [0] unused
     hipEvent_t batch_ev[movba::kMaxGroups + 1] = {};    // [0]: fork from the callers' stream, [g]: join of group g
     hipEvent_t batch_phase_ev[movba::kMaxGroups][movba::kPhaseEvents] = {};     // ring: end of group g's schur launch of trial t (t mod 16)
-    // pose-only scratch
-    char *pose_arena = nullptr;
-    size_t pose_cap = 0;
+    movba::Scratch pose_scratch;        // device scratch of the side calls (begin_side_call)
     // movba_lba_marginals (marginals.cpp): device scratch (controller, factor inverses, W, sigma, outputs) and the pinned image of
-    // the outputs, both grown on demand; the uploaded window's fixed flags (fixed keyframes get zero blocks)
-    char *marg = nullptr;
-    size_t marg_cap = 0;
-    char *marg_host = nullptr;
-    size_t marg_host_cap = 0;
+    // the outputs; the uploaded window's fixed flags (fixed keyframes get zero blocks)
+    movba::Scratch marg, marg_host{nullptr, 0, movba::Scratch::Pinned};
     std::vector<uint8_t> pose_fixed;
     movba::Worker packer;               // helper thread of movba_lba_upload
     // profiling

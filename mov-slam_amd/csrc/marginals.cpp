@@ -10,31 +10,6 @@
 
 using namespace movba;
 
-namespace {
-
-// the device scratch and the pinned image of the outputs, grown (never shrunk) like the arena
-int ensure_marg(movba_handle *h, size_t dev_bytes, size_t host_bytes)
-{
-    if (dev_bytes > h->marg_cap) {
-        if (h->marg) {
-            HIP_TRY(hipStreamSynchronize(h->stream));
-            HIP_TRY(hipFree(h->marg)); h->marg = nullptr; h->marg_cap = 0;
-        }
-        const size_t cap = align_up(dev_bytes + dev_bytes / 4, 1 << 20);
-        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&h->marg), cap));
-        h->marg_cap = cap;
-    }
-    if (host_bytes > h->marg_host_cap) {
-        if (h->marg_host) { HIP_TRY(hipHostFree(h->marg_host)); h->marg_host = nullptr; h->marg_host_cap = 0; }
-        const size_t cap = align_up(host_bytes + host_bytes / 4, 1 << 20);
-        HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&h->marg_host), cap, hipHostMallocDefault));
-        h->marg_host_cap = cap;
-    }
-    return MOVBA_OK;
-}
-
-}  // namespace
-
 extern "C" {
 
 int movba_lba_marginals(movba_handle *h, double damping, double *pose_cov, double *point_cov)
@@ -55,9 +30,10 @@ int movba_lba_marginals(movba_handle *h, double damping, double *pose_cov, doubl
     Carver oc;
     const size_t o_flags = oc.take<int32_t>(4), o_pose = oc.take<double>((size_t)NP * 36), o_pt = oc.take<double>((size_t)P * 9);
     const size_t out_bytes = point_cov ? oc.off : o_pt;
-    int rc = ensure_marg(h, o_out + oc.off, oc.off); if (rc) return rc;
+    // the device scratch and the pinned image of the outputs
+    int rc = h->marg.grow(h, o_out + oc.off); if (rc == MOVBA_OK) rc = h->marg_host.grow(h, oc.off); if (rc) return rc;
 
-    char *a = h->marg, *out = a + o_out;
+    char *a = h->marg.p, *out = a + o_out;
     MargDev m{};
     m.w = w;
     m.w.ctrl = reinterpret_cast<Ctrl *>(a + o_ctrl);
@@ -73,10 +49,10 @@ int movba_lba_marginals(movba_handle *h, double damping, double *pose_cov, doubl
     m.want_points = point_cov ? 1 : 0;
     m.pose_blocks = (NP + 255) / 256;
     HIP_TRY(launch_marginals(m, h->stream));
-    HIP_TRY(hipMemcpyAsync(h->marg_host, out, out_bytes, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->marg_host.p, out, out_bytes, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
 
-    const char *hb = h->marg_host;
+    const char *hb = h->marg_host.p;
     const int32_t *flags = reinterpret_cast<const int32_t *>(hb + o_flags);
     if (flags[0] || flags[1]) return MOVBA_SINGULAR;
     if (pose_cov) {

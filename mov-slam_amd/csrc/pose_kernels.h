@@ -31,7 +31,7 @@ size_t pose_ransac_bytes(int n_hyp);
 hipError_t configure_pose_kernels();
 hipError_t launch_pose_hyp(const PoseDev &p, hipStream_t s);      // the hypothesis stage as a grid of its own (inputs in device memory)
 hipError_t launch_pose_opt(const PoseDev &p, bool staged, hipStream_t s);
-// movba_pose_opt_batch (pose_batch.cpp): the same kernel bodies over n_frames frames of a device array, one workgroup per
+// movba_pose_opt_batch (pose_opt.cpp): the same kernel bodies over n_frames frames of a device array, one workgroup per
 // frame (LM: k_pose_opt_b) or per (frame, sample) (hypothesis stage: k_pose_hyp_b, n_blocks = hyp_first[n_frames], the prefix
 // sum of the frames' n_hyp).  staged: every frame's staged LDS need is at most lds_bytes <= 144 KB
 hipError_t launch_pose_hyp_batch(const PoseDev *frames, const int32_t *hyp_first, int n_frames, int n_blocks, hipStream_t s);

@@ -746,7 +746,7 @@ __device__ __forceinline__ void pose_opt_body(const PoseDev &p)
 template <bool STAGED>
 __global__ __launch_bounds__(kT) void k_pose_opt(PoseDev p) { pose_opt_body<STAGED>(p); }
 
-// movba_pose_opt_batch: workgroup f solves frame f (every frame's buffers are its own: pose_batch.cpp)
+// movba_pose_opt_batch: workgroup f solves frame f (every frame's buffers are its own: pose_opt.cpp)
 template <bool STAGED>
 __global__ __launch_bounds__(kT) void k_pose_opt_b(const PoseDev *__restrict__ frames) { pose_opt_body<STAGED>(frames[blockIdx.x]); }
 

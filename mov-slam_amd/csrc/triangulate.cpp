@@ -69,20 +69,9 @@ extern "C" int movba_triangulate(movba_handle *h, const movba_tri_desc *desc, mo
     const size_t total = c.off;
 
     res->status = MOVBA_ERR_HIP;            // (until the device work is through)
-    HIP_TRY(hipSetDevice(h->device));
-    if (h2d > h->pose_cap) {
-        if (h->pose_arena) { HIP_TRY(hipStreamSynchronize(h->stream)); HIP_TRY(hipFree(h->pose_arena)); h->pose_arena = nullptr; h->pose_cap = 0; }
-        const size_t cap = align_up(h2d + h2d / 4, 1 << 16);
-        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&h->pose_arena), cap));
-        h->pose_cap = cap;
-    }
-    int rc = ensure_stage(h, total); if (rc) return rc;
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    // (a window uploaded on this handle and not run yet: its arrays may still be crossing the bus out of the staging buffer)
-    HIP_TRY(hipEventSynchronize(h->copy_event));
-    h->export_in_run = false;        // (results a run may have left in the staging buffer are overwritten here: download exports again)
+    int rc = begin_side_call(h, h2d, total); if (rc) return rc;
 
-    char *sg = h->stage, *ar = h->pose_arena;
+    char *sg = h->stage, *ar = h->pose_scratch.p;
     put(sg, o_poses, d.poses, 7 * nv); put(sg, o_cam, d.cam, 4 * nv);
     if (stereo_views) { put(sg, o_bf, d.bf, nv); put(sg, o_b, d.b, nv); }
     put(sg, o_pv, d.pair_view, 2 * np); put(sg, o_pp, d.pair_ptr, np + 1);

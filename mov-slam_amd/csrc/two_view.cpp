@@ -16,7 +16,6 @@ using namespace movba;
 
 namespace {
 
-
 bool tv_desc_ok(const movba_two_view_desc &d, const movba_two_view_result &r)
 {
     if (d.n_matches < 0 || d.n_matches > MOVBA_MAX_TWO_VIEW_MATCHES) return false;
@@ -106,20 +105,9 @@ extern "C" int movba_two_view(movba_handle *h, const movba_two_view_desc *descs,
     const size_t total = c.off;
 
     for (int j = 0; j < n; ++j) results[j].status = MOVBA_ERR_HIP;      // (until the device work is through)
-    HIP_TRY(hipSetDevice(h->device));
-    if (dev_total > h->pose_cap) {
-        if (h->pose_arena) { HIP_TRY(hipStreamSynchronize(h->stream)); HIP_TRY(hipFree(h->pose_arena)); h->pose_arena = nullptr; h->pose_cap = 0; }
-        const size_t cap = align_up(dev_total + dev_total / 4, 1 << 16);
-        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&h->pose_arena), cap));
-        h->pose_cap = cap;
-    }
-    int rc = ensure_stage(h, total); if (rc) return rc;
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    // (a window uploaded on this handle and not run yet: its arrays may still be crossing the bus out of the staging buffer)
-    HIP_TRY(hipEventSynchronize(h->copy_event));
-    h->export_in_run = false;        // (results a run may have left in the staging buffer are overwritten here: download exports again)
+    int rc = begin_side_call(h, dev_total, total); if (rc) return rc;
 
-    char *sg = h->stage, *ar = h->pose_arena;
+    char *sg = h->stage, *ar = h->pose_scratch.p;
     struct View { unsigned long long *inl, *pts, *good, *code; };
     std::vector<View> views(np);
     for (int k = 0; k < n; ++k) {

@@ -129,17 +129,6 @@ struct EarlySetup {
     double t0;
 };
 
-// device scratch of the structure pass (h->scratch, h->scratch2) grown to `bytes`, never shrunk; the stream is drained first
-int grow_scratch(movba_handle *h, char *&buf, size_t &cap, size_t bytes)
-{
-    if (bytes <= cap) return MOVBA_OK;
-    if (buf) { HIP_TRY(hipStreamSynchronize(h->stream)); HIP_TRY(hipFree(buf)); buf = nullptr; cap = 0; }
-    const size_t c = align_up(bytes + bytes / 4, 1 << 20);
-    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&buf), c));
-    cap = c;
-    return MOVBA_OK;
-}
-
 struct Upload {
     movba_handle *const h;
     const movba_lba_desc *const d;
@@ -474,7 +463,7 @@ int Upload::group_on_device()
     edge_bytes = L.grouped_end;
     carve_state();
     int rc = carve_scratch(true); if (rc) return rc;
-    char *sa = h->scratch;
+    char *sa = h->scratch.p;
     // (the keyframes' flags are read out of host memory - the staging buffer is mapped -, through the place of the hessian
     //  indices, which the device makes itself here)
     std::memcpy(sg + L.hidx, d->pose_fixed, (size_t)NP);
@@ -645,13 +634,13 @@ int Upload::carve_scratch(bool basic)
     so_cntpt = sc.take<int32_t>(sorted_structure ? (size_t)P + 1 : 0);
     so_fixed = sc.take<uint8_t>(basic ? (size_t)NP + 4 : 0);
     so_H = sc.take<int32_t>(basic ? (size_t)((E + kBasicBlock - 1) / kBasicBlock) * NP : 0);
-    return grow_scratch(h, h->scratch, h->scratch_cap, sc.off);
+    return h->scratch.grow(h, sc.off);
 }
 
 // sd for this upload's structure pass: sizes and the scratch words of carve_scratch, then its arena addresses
 void Upload::start_struct_dev()
 {
-    char *sa = h->scratch;
+    char *sa = h->scratch.p;
     sd = StructDev{};
     sd.P = P; sd.nfree = nf; sd.NP = NP;
     if (!sorted_structure) { sd.nchunks = (P + 63) / 64; sd.cntw = reinterpret_cast<int32_t *>(sa + so_cntw); }
@@ -682,8 +671,8 @@ int Upload::launch_counts()
 {
     start_struct_dev();
     HIP_TRY(launch_struct_count(sd, h->stream));
-    const int rc = counts_out(dev_first ? reinterpret_cast<const int32_t *>(h->scratch + so_pe) : nullptr,
-                              dev_first ? reinterpret_cast<const int32_t *>(h->scratch + so_info) : nullptr);
+    const int rc = counts_out(dev_first ? reinterpret_cast<const int32_t *>(h->scratch.p + so_pe) : nullptr,
+                              dev_first ? reinterpret_cast<const int32_t *>(h->scratch.p + so_info) : nullptr);
     if (rc) return rc;
     // (the scan over the chunks is what the FILL needs, not the host: in direct mode the helper thread launches it with the fill)
     scan_pending = dev_first && direct_raw && h->opt.profile == 0;
@@ -715,7 +704,7 @@ int Upload::wait_for_counts()
 int Upload::structure_on_device()
 {
     int rc = carve_scratch(false); if (rc) return rc;
-    HIP_TRY(hipMemsetAsync(h->scratch + so_cnt, 0, so_err + 16 - so_cnt, h->stream));        // bin totals and the error word
+    HIP_TRY(hipMemsetAsync(h->scratch.p + so_cnt, 0, so_err + 16 - so_cnt, h->stream));        // bin totals and the error word
     rc = launch_counts(); if (rc) return rc;
     lap("edge H2D + count launches");
     return after_counts();
@@ -744,7 +733,7 @@ int Upload::after_counts()
                 HIP_TRY(hipMemcpyAsync(h->arena + L.base, sg + L.base, sizeof(int32_t) * NP, hipMemcpyHostToDevice, h->stream));
                 HIP_TRY(hipMemcpyAsync(h->arena + L.free_pose, sg + L.free_pose, sizeof(int32_t) * nf, hipMemcpyHostToDevice, h->stream));
             } else edge_b_stale = true;
-            HIP_TRY(hipMemsetAsync(h->scratch + so_cnt, 0, so_err + 16 - so_cnt, h->stream));
+            HIP_TRY(hipMemsetAsync(h->scratch.p + so_cnt, 0, so_err + 16 - so_cnt, h->stream));
             HIP_TRY(launch_struct_count(sd, h->stream));
             HIP_TRY(launch_struct_counts_out(sd, nullptr, 0, h->stream));
             HIP_TRY(launch_struct_scan(sd, h->stream));
@@ -797,9 +786,9 @@ int Upload::structure_on_device_sorted()
 {
     sorted_structure = true;
     int rc = carve_scratch(false); if (rc) return rc;
-    HIP_TRY(hipMemsetAsync(h->scratch + so_cnt, 0, so_err + 16 - so_cnt, h->stream));        // bin totals and the error word
+    HIP_TRY(hipMemsetAsync(h->scratch.p + so_cnt, 0, so_err + 16 - so_cnt, h->stream));        // bin totals and the error word
     start_struct_dev();
-    HIP_TRY(launch_couple_count(sd, reinterpret_cast<int32_t *>(h->scratch + so_cntpt), h->stream));
+    HIP_TRY(launch_couple_count(sd, reinterpret_cast<int32_t *>(h->scratch.p + so_cntpt), h->stream));
     rc = counts_out(nullptr, nullptr); if (rc) return rc;
     lap("edge H2D + count launches");
     rc = wait_for_counts(); if (rc) return rc;
@@ -814,7 +803,7 @@ int Upload::structure_on_device_sorted()
     s2_vals_in = s2.take<unsigned long long>(noff + 1);
     s2_tmp_bytes = sorted_fill_temp_bytes(P, (long long)noff, nf);
     s2_tmp = s2.take<char>(s2_tmp_bytes);
-    rc = grow_scratch(h, h->scratch2, h->scratch2_cap, s2.off); if (rc) return rc;
+    rc = h->scratch2.grow(h, s2.off); if (rc) return rc;
     if (c.off <= h->arena_cap && h->arena_gen == ho.arena_gen) {
         rc = queue_slots_and_fill(); if (rc) return rc;
         filled_early = true; fill_gen = h->arena_gen;
@@ -829,7 +818,7 @@ SlotPointLaunch Upload::slot_point_launch() const
     char *a = h->arena;
     return SlotPointLaunch{ reinterpret_cast<int32_t *>(a + L.slot), reinterpret_cast<const int32_t *>(a + L.gpose),
                             rank_mode ? reinterpret_cast<const int32_t *>(a + L.base) : nullptr, reinterpret_cast<const int32_t *>(a + L.gpoint),
-                            reinterpret_cast<int32_t *>(a + o_slotpt), E, dev_first ? reinterpret_cast<const int32_t *>(h->scratch + so_H) : nullptr, NP };
+                            reinterpret_cast<int32_t *>(a + o_slotpt), E, dev_first ? reinterpret_cast<const int32_t *>(h->scratch.p + so_H) : nullptr, NP };
 }
 
 // the fill as it is to be queued next: with the chunk scan in front where launch_counts left it to the fill (and then no more)
@@ -840,8 +829,8 @@ FillLaunch Upload::next_fill()
     f.scan_first = scan_pending;
     scan_pending = false;
     if (sorted_structure) {
-        char *s2 = h->scratch2;
-        f.cnt_pt = reinterpret_cast<const int32_t *>(h->scratch + so_cntpt); f.off = reinterpret_cast<int32_t *>(s2 + s2_off);
+        char *s2 = h->scratch2.p;
+        f.cnt_pt = reinterpret_cast<const int32_t *>(h->scratch.p + so_cntpt); f.off = reinterpret_cast<int32_t *>(s2 + s2_off);
         f.keys_in = reinterpret_cast<unsigned *>(s2 + s2_keys_in); f.keys_out = reinterpret_cast<unsigned *>(s2 + s2_keys_out);
         f.vals_in = reinterpret_cast<unsigned long long *>(s2 + s2_vals_in);
         f.tmp = s2 + s2_tmp; f.tmp_bytes = s2_tmp_bytes; f.noff = (long long)noff;

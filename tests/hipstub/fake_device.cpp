@@ -16,6 +16,7 @@
 
 #include "device_types.h"
 #include "kernels.h"
+#include "marginals.h"
 #include "pose_kernels.h"
 
 namespace {
@@ -382,5 +383,8 @@ hipError_t launch_pose_opt(const PoseDev &p, bool, hipStream_t s)
     });
     return hipSuccess;
 }
+
+// ---- marginals: linked because every binary holds the whole host side; no driver calls it (reports "not positive definite") ----
+hipError_t launch_marginals(const MargDev &m, hipStream_t s) { fake_enqueue(s, [m] { m.flags[0] = 1; m.flags[1] = 0; }); return hipSuccess; }
 
 }  // namespace movba

@@ -1,4 +1,4 @@
-// The fake device's side of movba_pose_opt_batch (mov-slam_amd/csrc/pose_batch.cpp): the two batched launch wrappers of
+// The fake device's side of movba_pose_opt_batch (mov-slam_amd/csrc/pose_opt.cpp): the two batched launch wrappers of
 // pose_kernels.h as closures on the fake stream (fake_hip.cpp).  They read EVERY byte each frame's PoseDev points to and write
 // its whole result record, so that the sanitizers see the host's layout and hand-offs; what they write is a function of the
 // frame's own inputs (pose0 echoed, chi2 from the observations, flags from the index), so a driver can tell whether each

@@ -1,4 +1,4 @@
-// Drives movba_pose_opt_batch's HOST side (mov-slam_amd/csrc/pose_batch.cpp) against the fake device of this directory
+// Drives movba_pose_opt_batch's HOST side (mov-slam_amd/csrc/pose_opt.cpp) against the fake device of this directory
 // (fake_device.cpp, fake_pose_batch.cpp), under AddressSanitizer + UndefinedBehaviorSanitizer or ThreadSanitizer: batches of
 // mixed frame sizes (frames beyond the LDS limit, frames with fewer than 4 matches, batches that make the staging buffer and
 // the pose arena grow between calls), invalid calls, a batch between an LBA upload and its run, and two threads on two

@@ -187,3 +187,63 @@ def test_batches_on_one_thread_while_another_solves_a_window(built_lib):
         assert not errs, errs[:3]
     finally:
         a.close(); b.close()
+
+
+def _side_calls(small):
+    """movba_pose_opt, movba_triangulate, movba_two_view, movba_pose_opt_batch and movba_pose_opt again, as functions of a
+    Solver.  small: at most 64 matches per frame or pair and 32 hypotheses (each call fits the 1 MiB the pose scratch and the
+    staging buffer start with).  Otherwise every call needs more than 1 MiB of both: a frame of 20 000 matches (57 bytes per
+    match on the device and in the staging buffer), 5 stereo pairs of 4 000 (64 bytes on the device, 89 in the staging
+    buffer), 6 frame pairs of 4 000 with 64 samples (41 bytes per match and 864 per sample on the device, 59 per match in the
+    staging buffer), 6 frames of 4 000 and one that is staged in LDS."""
+    n = 60 if small else 20000
+    first = dict(_frame(n, 200, 0), ransac_iters=20 if small else 32, ransac_seed=5, confidence=0.95, lo_iters=10)
+    last = _frame(n, 201, 1)            # (LM alone: staged in LDS when small, no device copy at all)
+    tri = synth.make_triangulation(2, 30, seed=71, stereo=True) if small else synth.make_triangulation(5, 4000, seed=72, stereo=True)
+    tv = [dict(synth.make_two_view(60 if small else 4000, seed=300 + k, scene=synth.TWO_VIEW_SCENES[k % 4]),
+               ransac_iters=32 if small else 64, ransac_seed=1 + k) for k in range(2 if small else 6)]
+    if small:
+        batch = [_frame(50, 210 + k, v) for k, v in enumerate((0, 1, 3))]
+    else:
+        batch = [_frame(4000, 220 + k, k % 5) for k in range(6)] + [_frame(500, 230, 2)]
+    return [lambda s: s.pose_opt(**first),
+            lambda s: s.triangulate(tri["views"], tri["pairs"], tri["matches"], tri["reproj_gate"], tri["far_threshold"]),
+            lambda s: s.two_view(tv),
+            lambda s: s.pose_opt_batch(batch),
+            lambda s: s.pose_opt(**last)]
+
+
+def _assert_same_bits(got, want, where):
+    if isinstance(want, list):
+        assert len(got) == len(want), where
+        for k, (g, w) in enumerate(zip(got, want)):
+            _assert_same_bits(g, w, f"{where}[{k}]")
+        return
+    assert got.keys() == want.keys(), where
+    for key in want:
+        g, w = np.atleast_1d(got[key]), np.atleast_1d(want[key])
+        assert g.dtype == w.dtype and g.shape == w.shape, (where, key)
+        # (raw bytes: rejected matches carry NaN points)
+        assert np.array_equal(np.ascontiguousarray(g).reshape(-1).view(np.uint8), np.ascontiguousarray(w).reshape(-1).view(np.uint8)), (where, key)
+
+
+def test_side_calls_interleaved_on_one_handle_give_a_fresh_handles_bits(built_lib):
+    """The four entry points that share the handle's pose scratch and staging buffer, one after the other on ONE handle: a
+    round of small calls, then a round in which every call needs more of both buffers than the first round left behind, so
+    the buffers are reallocated while they hold the other entry points' stale contents.  Every result array of every call is,
+    bit for bit, that of the same call on a fresh handle that has done nothing else."""
+    calls = _side_calls(True) + _side_calls(False)
+    want = []
+    for call in calls:
+        fresh = built_lib.Solver()
+        try:
+            want.append(call(fresh))
+        finally:
+            fresh.close()
+    one = built_lib.Solver()
+    try:
+        got = [call(one) for call in calls]
+    finally:
+        one.close()
+    for k, (g, w) in enumerate(zip(got, want)):
+        _assert_same_bits(g, w, f"call {k}")

@@ -386,31 +386,24 @@ def test_symbol_is_exported_and_refuses_null(built_lib):
 
 # ---- host side under the sanitizers ------------------------------------------------------------------------------------
 STUB = os.path.join(ROOT, "tests", "hipstub")
-CS = os.path.join(ROOT, "mov-slam_amd", "csrc")
-SRCS = [os.path.join(CS, f) for f in ("api.cpp", "upload.cpp", "structure.cpp", "dense_plan.cpp", "pcg_plan.cpp", "triangulate.cpp")] + \
-       [os.path.join(STUB, f) for f in ("fake_hip.cpp", "fake_device.cpp", "fake_triangulate.cpp", "triangulate_driver.cpp")]
 
 
-def _build_and_run(tmp_path, sanitize, env):
-    exe = str(tmp_path / "triangulate_driver")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", *sanitize, "-fno-omit-frame-pointer", "-I" + STUB,
-                           "-I" + os.path.join(ROOT, "include"), "-I" + CS, "-Wall", "-Wno-unused-function", "-Wno-unknown-pragmas",
-                           *SRCS, "-o", exe, "-lpthread"])
-    return subprocess.run([exe], env=dict(os.environ, **env), capture_output=True, text=True, timeout=600)
+def _build_and_run(target, env):
+    subprocess.check_call(["make", "-C", STUB, "-s", target])
+    return subprocess.run([os.path.join(STUB, target)], env=dict(os.environ, **env), capture_output=True, text=True, timeout=600)
 
 
-def test_triangulate_host_side_under_address_and_undefined_behaviour_sanitizers(tmp_path):
+def test_triangulate_host_side_under_address_and_undefined_behaviour_sanitizers():
     """Every invalid descriptor is refused before anything is written; calls that grow and shrink (staging buffer and device
     scratch regrown between them), pinned and ordinary result arrays, empty pairs; a call between an LBA upload and its run
     leaves the run's results unchanged; two threads on two handles.  The fake device runs the library's own per-match
     arithmetic (triangulate_math.h) on the CPU, so the driver also checks recovered points and codes."""
-    p = _build_and_run(tmp_path, ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"],
-                       {"ASAN_OPTIONS": "detect_leaks=0 abort_on_error=0 exitcode=67", "UBSAN_OPTIONS": "print_stacktrace=1"})
+    p = _build_and_run("triangulate_asan", {"ASAN_OPTIONS": "detect_leaks=0 abort_on_error=0 exitcode=67", "UBSAN_OPTIONS": "print_stacktrace=1"})
     assert "ERROR: AddressSanitizer" not in p.stderr and "runtime error:" not in p.stderr, p.stderr[:4000]
     assert p.returncode == 0 and p.stdout.strip().endswith("TRIANGULATE OK"), p.stderr[-2000:]
 
 
-def test_triangulate_host_side_is_race_free(tmp_path):
-    p = _build_and_run(tmp_path, ["-fsanitize=thread"], {"TSAN_OPTIONS": "halt_on_error=0 exitcode=66"})
+def test_triangulate_host_side_is_race_free():
+    p = _build_and_run("triangulate_tsan", {"TSAN_OPTIONS": "halt_on_error=0 exitcode=66"})
     assert "WARNING: ThreadSanitizer" not in p.stderr, p.stderr[:4000]
     assert p.returncode == 0 and p.stdout.strip().endswith("TRIANGULATE OK"), p.stderr[-2000:]

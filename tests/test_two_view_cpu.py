@@ -677,31 +677,25 @@ def test_symbols_constants_and_the_sampler(built_lib):
 
 # ---- host side and the library's own arithmetic over the fake device --------------------------------------------------------
 STUB = os.path.join(ROOT, "tests", "hipstub")
-CS = os.path.join(ROOT, "mov-slam_amd", "csrc")
-SRCS = [os.path.join(CS, f) for f in ("api.cpp", "upload.cpp", "structure.cpp", "dense_plan.cpp", "pcg_plan.cpp", "two_view.cpp")] + \
-       [os.path.join(STUB, f) for f in ("fake_hip.cpp", "fake_device.cpp", "fake_two_view.cpp", "two_view_driver.cpp")]
 
 
-def _build(tmp_path, sanitize, opt="-O1"):
-    exe = str(tmp_path / "two_view_driver")
-    subprocess.check_call(["g++", "-std=c++17", opt, "-g", *sanitize, "-fno-omit-frame-pointer", "-I" + STUB,
-                           "-I" + os.path.join(ROOT, "include"), "-I" + CS, "-Wall", "-Wno-unused-function", "-Wno-unknown-pragmas",
-                           *SRCS, "-o", exe, "-lpthread"])
-    return exe
+def _build(target):
+    subprocess.check_call(["make", "-C", STUB, "-s", target])
+    return os.path.join(STUB, target)
 
 
-def test_two_view_host_side_under_address_and_undefined_behaviour_sanitizers(tmp_path):
+def test_two_view_host_side_under_address_and_undefined_behaviour_sanitizers():
     """Every invalid descriptor refused with canaries untouched, n == 0, pairs under 5 matches, pinned and ordinary result
     arrays, batches against solo calls bit for bit, a call between an LBA upload and its run, two threads on two handles."""
-    exe = _build(tmp_path, ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"])
+    exe = _build("two_view_asan")
     p = subprocess.run([exe], env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0 abort_on_error=0 exitcode=67", UBSAN_OPTIONS="print_stacktrace=1"),
                        capture_output=True, text=True, timeout=900)
     assert "ERROR: AddressSanitizer" not in p.stderr and "runtime error:" not in p.stderr, p.stderr[:4000]
     assert p.returncode == 0 and p.stdout.strip().endswith("TWO_VIEW OK"), p.stderr[-2000:]
 
 
-def test_two_view_host_side_is_race_free(tmp_path):
-    exe = _build(tmp_path, ["-fsanitize=thread"])
+def test_two_view_host_side_is_race_free():
+    exe = _build("two_view_tsan")
     p = subprocess.run([exe], env=dict(os.environ, TSAN_OPTIONS="halt_on_error=0 exitcode=66"), capture_output=True, text=True, timeout=900)
     assert "WARNING: ThreadSanitizer" not in p.stderr, p.stderr[:4000]
     assert p.returncode == 0 and p.stdout.strip().endswith("TWO_VIEW OK"), p.stderr[-2000:]
@@ -710,7 +704,7 @@ def test_two_view_host_side_is_race_free(tmp_path):
 def test_the_librarys_own_solver_against_the_restatement_on_the_cpu(tmp_path):
     """The fake device runs two_view_math.h: the driver solves pairs written to a file and writes results back; the same
     comparison, tolerances and caps as on the GPU."""
-    exe = _build(tmp_path, [], "-O2")
+    exe = _build("two_view_opt")
     n_tie = 0
     picked = SCENES[::4]
     for label, args, iters, seed in picked:
