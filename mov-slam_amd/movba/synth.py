@@ -374,6 +374,73 @@ def mixed_cameras(w: Window, seed: int, models=((320.0, 320.0, 320.0, 240.0), (4
     return out
 
 
+# ---------------------------------------------------------------------------------------------
+# A change of world frame.  Every generator in this file builds its cameras as small rotations about the identity (a yaw
+# about y, a few hundredths of a radian per axis): quaternions with w ~ 1, rotation matrices with positive trace.  For a rigid
+# motion G = (Rg, tg) the points become X' = Rg X + tg and the poses Tcw' = Tcw o G^-1 (R' = R Rg^T, t' = t - R' tg); the
+# observations stay.  It is the same optimisation problem, posed with cameras in general position.  The transform is made
+# in double and nothing is rounded to float32 again, so a solver's result maps back to the un-gauged one to rounding.
+# G^-1 = (Rg^T, -Rg^T tg) maps back.
+# ---------------------------------------------------------------------------------------------
+def gauge_rotation(axis, angle_deg: float):
+    """Rotation by angle_deg about `axis` (any length)."""
+    a = np.asarray(axis, np.float64)
+    return _rodrigues(np.deg2rad(angle_deg) * a / np.linalg.norm(a))
+
+
+def regauge_points(X, Rg, tg=(0.0, 0.0, 0.0)):
+    return np.asarray(X, np.float64) @ np.asarray(Rg).T + np.asarray(tg, np.float64)
+
+
+def regauge_poses(poses, Rg, tg=(0.0, 0.0, 0.0), flip_every: int = 0, renormalise: bool = True):
+    """(N, 7) poses Tcw in the new world frame.  The quaternions come back unit with w >= 0, except: flip_every = n negates
+    the quaternion of every n-th pose (1, 1 + n, ...: the same rotation, w < 0); renormalise=False scales every quaternion by
+    the norm its float32 rounding has (off unit by ~3e-8: what a caller that widens a float quaternion hands over; the
+    direction stays the exact one)."""
+    poses = np.asarray(poses, np.float64)
+    tg = np.asarray(tg, np.float64)
+    out = np.zeros_like(poses)
+    for i, p in enumerate(poses):
+        R2 = R_from_quat(p[:4] / np.linalg.norm(p[:4])) @ np.asarray(Rg).T
+        q = quat_from_R(R2)
+        out[i, 4:] = p[4:] - R_from_quat(q) @ tg
+        if flip_every and i % flip_every == flip_every - 1:
+            q = -q
+        if not renormalise:
+            q = q * np.linalg.norm(_f32(q))
+        out[i, :4] = q
+    return out
+
+
+def regauge(w: Window, Rg, tg=(0.0, 0.0, 0.0), flip_every: int = 0, renormalise: bool = True) -> Window:
+    """The window `w` in the world frame moved by G = (Rg, tg): estimates and truth follow, everything else is shared."""
+    import dataclasses
+    meta = dict(w.meta); meta["regauged"] = True
+    return dataclasses.replace(
+        w, poses=regauge_poses(w.poses, Rg, tg, flip_every, renormalise), points=regauge_points(w.points, Rg, tg),
+        truth_poses=None if w.truth_poses is None else regauge_poses(w.truth_poses, Rg, tg),
+        truth_points=None if w.truth_points is None else regauge_points(w.truth_points, Rg, tg), meta=meta)
+
+
+def regauge_frame(f: dict, Rg, tg=(0.0, 0.0, 0.0), flip: bool = False, renormalise: bool = True) -> dict:
+    """A make_frame() operand in the moved world frame: Xw, pose0 and truth follow."""
+    out = dict(f)
+    out["Xw"] = regauge_points(f["Xw"], Rg, tg)
+    out["pose0"] = regauge_poses(f["pose0"][None], Rg, tg, 1 if flip else 0, renormalise)[0]
+    out["truth"] = regauge_poses(f["truth"][None], Rg, tg)[0]
+    return out
+
+
+def regauge_triangulation(sc: dict, Rg, tg=(0.0, 0.0, 0.0), flip_every: int = 0) -> dict:
+    """A make_triangulation() scene in the moved world frame: the views' poses and the truth follow.  (The DLT minimises
+    over unit homogeneous 4-vectors: a rotation of the world is orthogonal on them and leaves its result alone, a translation
+    is not and changes what ill-posed matches give - in the reference too.)"""
+    out = dict(sc)
+    out["views"] = dict(sc["views"], poses=regauge_poses(sc["views"]["poses"], Rg, tg, flip_every))
+    out["truth"] = regauge_points(sc["truth"], Rg, tg)
+    return out
+
+
 def pattern_cfg(name: str, seed: int | None = None) -> Window:
     """cfg3-sized windows (50 + 10 keyframes x 20 000 map points) of the other covisibility patterns."""
     if name == "hub":
@@ -527,12 +594,14 @@ TWO_VIEW_SCENES = ("general", "planar", "rotation", "forward")
 
 
 def make_two_view(n_matches: int, inlier_frac: float = 0.7, noise_px: float = 0.5, seed: int = 0, scene: str = "general",
-                  cam=(458.0, 457.0, 367.0, 248.0), width: int = 752, height: int = 480) -> dict:
+                  cam=(458.0, 457.0, 367.0, 248.0), width: int = 752, height: int = 480, roll_deg: float = 0.0) -> dict:
     """One frame pair for movba_two_view: camera 1 at the origin, camera 2 at T21 = (R, t) with |t| = 1 (the unit the call
     returns), points seen by both, noise_px of Gaussian noise on both observations; 1 - inlier_frac of the matches are gross
     mismatches (the second observation anywhere in the image).  Scenes: `general` - depths of 4 - 40 baselines, sideways
     motion with a few degrees of rotation; `planar` - every point on one slanted plane (the case an eight-point solver cannot
     do); `rotation` - zero baseline (no parallax: initialisation must fail); `forward` - motion along the optical axis.
+    roll_deg: camera 2 turned by this angle about its own optical axis on top of the scene's motion (R <- Rz R, t <- Rz t,
+    before projection; the returned truth includes it): 180 degrees gives a T21 whose rotation has trace ~ -1.
     -> dict(obs1, obs2 (M, 2), cam, R (3, 3), t (3,): the true T21 (t = 0 for `rotation`), X (M, 3): the points in camera 1,
     is_inlier (M,))."""
     assert scene in TWO_VIEW_SCENES
@@ -560,6 +629,9 @@ def make_two_view(n_matches: int, inlier_frac: float = 0.7, noise_px: float = 0.
     t = t / np.linalg.norm(t)
     if scene == "rotation":
         t = np.zeros(3)
+    if roll_deg != 0.0:
+        Rz = _rodrigues(np.array([0.0, 0.0, np.deg2rad(roll_deg)]))
+        R = Rz @ R; t = Rz @ t
     Y = X @ R.T + t
     obs1 = np.stack([u, v], 1) + rng.normal(0, noise_px, (M, 2)) if noise_px > 0 else np.stack([u, v], 1)
     obs2 = np.stack([fx * Y[:, 0] / Y[:, 2] + cx, fy * Y[:, 1] / Y[:, 2] + cy], 1)

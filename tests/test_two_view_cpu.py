@@ -288,8 +288,7 @@ def check_rt(R, t, cam, obs1, obs2, inlier, th2):
 
 
 def R2q(R):
-    w = math.sqrt(max(0.0, 1 + R[0, 0] + R[1, 1] + R[2, 2])) / 2          # (rotations of a few degrees: w is far from 0)
-    return np.array([(R[2, 1] - R[1, 2]) / (4 * w), (R[0, 2] - R[2, 0]) / (4 * w), (R[1, 0] - R[0, 1]) / (4 * w), w])
+    return synth.quat_from_R(np.asarray(R, float))          # (by the largest diagonal entry where the trace is not positive: accurate at w ~ 0)
 
 
 def hypotheses_ref(pair, samples, solver="poly", threshold=1.0):
@@ -587,11 +586,11 @@ def test_one_focal_length_quirk_shows_on_a_camera_with_unequal_focal_lengths():
 
 
 # ---- the tolerances and the caps ----------------------------------------------------------------------------------------
-def _measure():
+def _measure(scenes=None):
     e_spread = pose_spread = pos_spread = loss_spread = par_spread = 0.0
     n_tie = 0
-    rows = []
-    for label, args, iters, seed in SCENES:
+    rows, so_far = [], []               # (so_far: the running maxima of pose, point and parallax spread after every scene)
+    for label, args, iters, seed in (SCENES if scenes is None else scenes):
         p = synth.make_two_view(**args)
         samples = samples_ref(args["n_matches"], iters, seed)
         ha, hb = hypotheses_ref(p, samples, "poly"), hypotheses_ref(p, samples, "action")
@@ -619,7 +618,8 @@ def _measure():
             pos_spread = max(pos_spread, float((np.linalg.norm(ra["points"][both] - rb["points"][both], axis=1) /
                                                 np.linalg.norm(ra["points"][both], axis=1)).max()))
         rows.append((label, n_c, n_ill, int(edge.sum()), len(edge), tie, ra["outcome"]))
-    return dict(e=e_spread, pose=pose_spread, pos=pos_spread, loss=loss_spread, par=par_spread, n_tie=n_tie, rows=rows)
+        so_far.append((pose_spread, pos_spread, par_spread))
+    return dict(e=e_spread, pose=pose_spread, pos=pos_spread, loss=loss_spread, par=par_spread, n_tie=n_tie, rows=rows, so_far=so_far)
 
 
 _measured = {}
@@ -701,35 +701,41 @@ def test_two_view_host_side_is_race_free():
     assert p.returncode == 0 and p.stdout.strip().endswith("TWO_VIEW OK"), p.stderr[-2000:]
 
 
+def solve_on_the_fake_device(p, iters, seed, tmp_path):
+    """one pair through the driver of tests/hipstub that runs the library's two_view_math.h on the CPU -> a result with diagnostics"""
+    exe = _build("two_view_opt")
+    fin, fout = str(tmp_path / "in.bin"), str(tmp_path / "out.bin")
+    M = len(p["obs1"])
+    with open(fin, "wb") as fh:
+        np.array([M, iters, seed], np.int32).tofile(fh)
+        np.array(p["cam"], np.float64).tofile(fh)
+        np.ascontiguousarray(p["obs1"], np.float64).tofile(fh); np.ascontiguousarray(p["obs2"], np.float64).tofile(fh)
+    subprocess.check_call([exe, fin, fout], timeout=600)
+    raw = np.fromfile(fout, np.float64)
+    k = 0
+
+    def take(n):
+        nonlocal k
+        v = raw[k:k + n]; k += n
+        return v
+    head = take(24)
+    got = dict(pose=head[:7], E=head[7:16].reshape(3, 3), parallax_deg=head[16], outcome=int(head[17]), n_inliers=int(head[18]),
+               n_pass=int(head[19]), n_good=int(head[20]), samples_used=int(head[21]), status=int(head[22]))
+    got["inlier"] = take(M).astype(np.uint8); got["good"] = take(M).astype(np.uint8); got["code"] = take(M).astype(np.uint8)
+    got["points"] = take(3 * M).reshape(M, 3)
+    got["hyp_nsol"] = take(iters).astype(np.int32); got["hyp_E"] = take(90 * iters).reshape(iters, 10, 3, 3)
+    got["hyp_loss"] = take(10 * iters).reshape(iters, 10)
+    return got
+
+
 def test_the_librarys_own_solver_against_the_restatement_on_the_cpu(tmp_path):
     """The fake device runs two_view_math.h: the driver solves pairs written to a file and writes results back; the same
     comparison, tolerances and caps as on the GPU."""
-    exe = _build("two_view_opt")
     n_tie = 0
     picked = SCENES[::4]
     for label, args, iters, seed in picked:
         p = synth.make_two_view(**args)
-        fin, fout = str(tmp_path / "in.bin"), str(tmp_path / "out.bin")
-        M = args["n_matches"]
-        with open(fin, "wb") as fh:
-            np.array([M, iters, seed], np.int32).tofile(fh)
-            np.array(p["cam"], np.float64).tofile(fh)
-            np.ascontiguousarray(p["obs1"], np.float64).tofile(fh); np.ascontiguousarray(p["obs2"], np.float64).tofile(fh)
-        subprocess.check_call([exe, fin, fout], timeout=600)
-        raw = np.fromfile(fout, np.float64)
-        k = 0
-
-        def take(n):
-            nonlocal k
-            v = raw[k:k + n]; k += n
-            return v
-        head = take(24)
-        got = dict(pose=head[:7], E=head[7:16].reshape(3, 3), parallax_deg=head[16], outcome=int(head[17]), n_inliers=int(head[18]),
-                   n_pass=int(head[19]), n_good=int(head[20]), samples_used=int(head[21]), status=int(head[22]))
-        got["inlier"] = take(M).astype(np.uint8); got["good"] = take(M).astype(np.uint8); got["code"] = take(M).astype(np.uint8)
-        got["points"] = take(3 * M).reshape(M, 3)
-        got["hyp_nsol"] = take(iters).astype(np.int32); got["hyp_E"] = take(90 * iters).reshape(iters, 10, 3, 3)
-        got["hyp_loss"] = take(10 * iters).reshape(iters, 10)
+        got = solve_on_the_fake_device(p, iters, seed, tmp_path)
         assert got["status"] == 0
         n_tie += compare_with_ref(got, p, iters, seed, label, check_truth=True)["tie"]
     assert n_tie <= max(TIE_CAP * len(picked), 0)
