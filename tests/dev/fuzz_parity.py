@@ -12,7 +12,7 @@ from oracle import oracle
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import fuzz_gen
 sys.path.insert(0, os.path.join(ROOT, "tests"))
-from conftest import oracle_order_noise
+import order_noise
 
 rng = np.random.default_rng(int(sys.argv[1]) if len(sys.argv) > 1 else 0)
 n = int(sys.argv[2]) if len(sys.argv) > 2 else 60
@@ -32,13 +32,13 @@ for it in range(n):
     # by cond(S) * eps in the weak directions) and counted as mismatches like every other window when they exceed it
     per_kf = np.bincount(w.edge_pose, minlength=w.n_poses)[w.pose_fixed == 0]
     weak = per_kf.min() < 12 if len(per_kf) else True
-    tol_q, tol_t, tol_p = (1e-6, 1e-6, 1e-4) if weak else (1e-8, 1e-8, 1e-6)
+    usual = order_noise.usual(w)                      # (the classes live in tests/order_noise.py, shared with the parity tests)
+    tol_q, tol_t, tol_p = usual["rot"], usual["trans"], usual["point"]
     # a free keyframe with fewer than three observations has no unique pose at all (six unknowns from < 6 equations): the
     # reduced matrix is singular but for the LM damping, two exact solvers land anywhere along the free directions
     # (seed 21, window 474: 130 keyframes x 200 points, one observation on some keyframes: both direct solvers 1e-5 m from the
     # oracle, costs equal to six digits).  Such windows are held to the cost trace instead of the poses.
     degenerate = len(per_kf) > 0 and per_kf.min() < 3
-    if degenerate: tol_q, tol_t, tol_p = 1e-3, 1e-3, 1e-2
     ro = oracle.solve(w)
     try:
         rg = s.solve(w)
@@ -54,8 +54,7 @@ for it in range(n):
     f0, f1 = ro['trace']['f0'], ro['trace']['f1']
     # ... and so are decisions at a cost 18 orders of magnitude under the initial one (a noise-free window solved to the last
     # bit: residuals of 1e-13 px, whose squares are rounding noise in absolute terms)
-    nz = np.flatnonzero((np.abs(f0 - f1) <= 1e-9 * np.abs(f0)) | (f0 <= 1e-18 * f0[0]))
-    k0 = int(nz[0]) if len(nz) else len(f0)
+    k0 = order_noise.noise_floor_trial(ro)
     same = np.array_equal(ro['trace']['accept'][:k0], rg['trace']['accept'][:k0]) and (k0 < len(f0) or ro['n_solves'] == rg['n_solves'])
     ok = dq < tol_q and dt < tol_t and pt < tol_p and outl == 0 and same
     if degenerate: ok = ok and np.allclose(ro['trace']['f1'][:k0], rg['trace']['f1'][:k0], rtol=1e-4)
@@ -64,12 +63,16 @@ for it in range(n):
         print(f"[{it}] close to tolerance: K={K} F={F} P={P} run {lo}-{hi} stereo {stereo} seed {seed}: dq {dq:.2e} dt {dt:.2e} pt {pt:.2e} pcg {rg['pcg_iters']} per trial {rg['trace']['pcg'].tolist()}", flush=True)
     if not ok and outl == 0 and same and not degenerate:
         # beyond the tolerance of its class: how far does the ORACLE move when a map point's edges are added in another order
-        # (the reference's own run-to-run freedom, conftest.oracle_order_noise)?  Inside three times that spread the window
-        # says nothing about the solver.
-        nq, nt, npt = oracle_order_noise(oracle, w, n=4)
-        if dq <= max(tol_q, 3 * nq) and dt <= max(tol_t, 3 * nt) and pt <= max(tol_p, 3 * npt):
+        # (the reference's own run-to-run freedom)?  Inside three times that spread - in the poses, the points, the lambda and
+        # cost traces and the per-edge chi2: order_noise.spread and tolerances, the rule of the parity tests - the window says
+        # nothing about the solver.
+        sp = order_noise.spread(oracle, w, n=16, cache=False)
+        tol = order_noise.tolerances(w, sp)
+        d = order_noise.distances(rg, ro, w)
+        if dq <= tol["rot"] and d["trans"] <= tol["trans"] and d["point"] <= tol["point"] and d["lam_rtol"] <= tol["lam_rtol"] \
+                and d["f1_rtol"] <= tol["f1_rtol"] and d["chi2_tol"] <= tol["chi2_tol"][0] and sp.same_decisions:
             noisy += 1
-            print(f"[{it}] ORDER-NOISE K={K} F={F} P={P} run {lo}-{hi} stereo {stereo} seed {seed}: dq {dq:.2e} dt {dt:.2e} pt {pt:.2e} against the oracle's own spread {nq:.2e} {nt:.2e} {npt:.2e} (band trials {rg['n_band']}, direct {rg['n_direct']})", flush=True)
+            print(f"[{it}] ORDER-NOISE K={K} F={F} P={P} run {lo}-{hi} stereo {stereo} seed {seed}: dq {dq:.2e} dt {dt:.2e} pt {pt:.2e} lam {d['lam_rtol']:.2e} f1 {d['f1_rtol']:.2e} chi2 {d['chi2_tol']:.2e} against the oracle's own spread {sp.rot:.2e} {sp.trans:.2e} {sp.point:.2e} {sp.lam:.2e} {sp.f1:.2e} {sp.chi2:.2e} (band trials {rg['n_band']}, direct {rg['n_direct']})", flush=True)
             continue
     if it % 50 == 49:
         print(f"[{it}] ... {it + 1} windows, {bad} mismatches, {noisy} inside the oracle's edge-order spread so far", flush=True)
