@@ -486,7 +486,19 @@ typedef struct {
  *  2. Score.  Every candidate on all matches: squared Sampson distance in pixels, sigma-consensus++ loss (MAGSAC++, as
  *     movba_pose_opt) with gate threshold^2.  Winner: lowest loss among the samples the stopping rule admits, N = log(1 -
  *     confidence) / log(1 - w^5) with w the inlier ratio of the best candidate so far; ties go to the lower (sample, root) index.
- *     inlier0[m] = Sampson^2 <= threshold^2, n_inliers = their number.  There is NO local optimisation / refit of the winner.
+ *     inlier0[m] = Sampson^2 <= threshold^2, n_inliers = their number.  movba_two_view does not refit the winner;
+ *     movba_two_view_lo (below) does: stage 2b.
+ *  2b. (movba_two_view_lo with lo_iters > 0 only.)  Local optimisation of the winner E0: iteratively reweighted Gauss-Newton with the
+ *     sigma-consensus++ weights of ALL matches (MAGSAC++'s refit; restated by these rules, not OpenCV's bits).  Start: (R, t) of
+ *     E0's decomposition, of its two rotations the one with the larger trace (the first on equal traces), t with the
+ *     sign that makes <[t]x R, E0> >= 0 (the iterates do not depend on it beyond rounding).  Parameters: E = [t]x R,
+ *     |t| = 1; a step (d omega, d tau) is R <- exp([d omega]x) R, t <- normalise(t + d tau_1 b1 + d tau_2 b2) with b1 = normalise(t x e_k),
+ *     k the index of the smallest |t_k| (the lowest on a tie), b2 = t x b1.  Residual: the SIGNED Sampson distance in pixels, its
+ *     1 x 5 Jacobian exact.  Pass k = 0 .. lo_iters over all matches at iterate k: L_k = sum of the losses (gate threshold^2; iterate 0
+ *     is E0 itself); for k < lo_iters, H = sum w J J^T, g = sum w J r, step -H^-1 g by Cholesky without damping; a pivot that is not
+ *     positive and finite ends the refit.  Kept: the iterate with the lowest L_k, the lowest k on a tie - so loss <= loss0 - handed
+ *     out as [t]x R with the sign that makes <E, E0> >= 0, or as E0 itself, bit for bit, for k = 0.  inlier0, n_inliers and stages
+ *     3 and 4 then run on the kept E; samples_used and the hypothesis tables stay those of stages 1 and 2.
  *  3. Pose recovery.  SVD of E (one-sided Jacobi), the four (R, t) with det R = +1; for each, every inlier0 match is triangulated
  *     linearly over [I | 0], [R | t] in f-normalised coordinates and counted when 0 < z1 < max_depth and 0 < z2 < max_depth; the
  *     largest count wins, ties in the order (R1, t), (R2, t), (R1, -t), (R2, -t).  n_pass = that count, inlier = inlier0 AND the test.
@@ -509,6 +521,28 @@ int  movba_two_view(movba_handle *h, const movba_two_view_desc *descs, movba_two
 /* The minimal samples movba_two_view draws for (n_matches >= 5, n_hyp, seed): n_hyp x 5 distinct match indices, from the
  * generator of movba_pose_ransac_samples on another stream.  Host only. */
 int  movba_two_view_samples(int32_t n_matches, int32_t n_hyp, uint32_t seed, int32_t *out);
+
+/* movba_two_view with the local optimisation of the winner (stage 2b above): what cv::USAC_MAGSAC does with its best model and
+ * movba_pose_opt does with lo_iters.  10 steps is the setting examined in DESIGN.md. */
+#define MOVBA_MAX_TWO_VIEW_LO_ITERS 32
+typedef struct {
+    double  loss0;        /* sigma-consensus++ loss (sum over the pair's matches, as hyp_loss) of the minimal-sample winner     */
+    double  loss;         /* ... of the iterate that was kept: loss <= loss0                                                   */
+    double  E0[9];        /* the minimal-sample winner: bit for bit what movba_two_view returns as E                           */
+    int32_t kept;         /* 0: the winner itself was kept; k: the iterate after k steps                                       */
+    int32_t steps;        /* steps taken, <= lo_iters (fewer: the 5 x 5 system was not positive definite or not finite)        */
+    int32_t n_inliers0;   /* matches within threshold of E0: movba_two_view's n_inliers                                        */
+    int32_t pad;
+} movba_two_view_lo_info;   /* 104 bytes */
+/* Conventions, checks, statuses, batch limit, pinned result memory and handle sharing as movba_two_view, which is this call with
+ * lo_iters = 0 and info = NULL.  lo_iters outside 0 .. MOVBA_MAX_TWO_VIEW_LO_ITERS: MOVBA_ERR_ARG, nothing written except
+ * `status`.  lo_iters == 0: the results of movba_two_view bit for bit, info[i] = { loss0, loss0, E, 0, 0, n_inliers }.  info: n
+ * entries or NULL; a pair without a model (MOVBA_TV_NO_MODEL, MOVBA_EMPTY) gets a zeroed entry.  One launch more than
+ * movba_two_view (k_tv_lo, one workgroup per pair, between k_tv_hyp and k_tv_recover) when lo_iters > 0, and one small copy
+ * back before the synchronisation.  No floating-point atomics: a pair's result, `info` included, does not depend on the other
+ * pairs or their order, and two calls give the same bits. */
+int  movba_two_view_lo(movba_handle *h, const movba_two_view_desc *descs, movba_two_view_result *results, int32_t n,
+                       int32_t lo_iters, movba_two_view_lo_info *info /* n, or NULL */);
 
 #ifdef __cplusplus
 }

@@ -1,9 +1,11 @@
-// movba_two_view (include/movba.h): monocular map initialisation for many frame pairs in one call.  The device pass is
-// two_view.hip (three kernels); this file checks every descriptor, packs pairs + matches + samples into the handle's staging
+// movba_two_view and movba_two_view_lo (include/movba.h): monocular map initialisation for many frame pairs in one call, without
+// and with the local optimisation of the winner; both are one front (two_view_front).  The device pass is two_view.hip (three
+// kernels, and k_tv_lo for the refit); this file checks every descriptor, packs pairs + matches + samples into the handle's staging
 // buffer, sends them with ONE copy, queues the launches and hands the results over after ONE synchronisation.  Per-match
 // result arrays that lie in movba_host_alloc memory are written by the kernels themselves; others arrive in the staging
 // buffer and are copied out.  The hypothesis tables (hyp_nsol / hyp_E / hyp_loss) stay in device scratch and are copied
-// only for a caller that asks for them.
+// only for a caller that asks for them.  The refit's per-pair slots (TvDev::lo) exist only when a refit or `info` is asked
+// for: they go up zero-filled with the inputs and come back with one copy more before the synchronisation.
 #include <cmath>
 #include <cstring>
 #include <vector>
@@ -53,13 +55,17 @@ extern "C" int movba_two_view_samples(int32_t n, int32_t n_hyp, uint32_t seed, i
     return MOVBA_OK;
 }
 
-extern "C" int movba_two_view(movba_handle *h, const movba_two_view_desc *descs, movba_two_view_result *results, int32_t n)
+namespace {
+
+int two_view_front(movba_handle *h, const movba_two_view_desc *descs, movba_two_view_result *results, int32_t n, int32_t lo_iters,
+                   movba_two_view_lo_info *info)
 {
     if (!h || n < 0 || n > MOVBA_MAX_TWO_VIEW_BATCH) return MOVBA_ERR_ARG;
-    if (n == 0) return MOVBA_OK;
+    const bool lo_ok = lo_iters >= 0 && lo_iters <= MOVBA_MAX_TWO_VIEW_LO_ITERS;
+    if (n == 0) return lo_ok ? MOVBA_OK : MOVBA_ERR_ARG;
     if (!descs || !results) return MOVBA_ERR_ARG;
     for (int k = 0; k < n; ++k)
-        if (!tv_desc_ok(descs[k], results[k])) {
+        if (!lo_ok || !tv_desc_ok(descs[k], results[k])) {
             for (int j = 0; j < n; ++j) results[j].status = MOVBA_ERR_ARG;
             return MOVBA_ERR_ARG;
         }
@@ -94,6 +100,9 @@ extern "C" int movba_two_view(movba_handle *h, const movba_two_view_desc *descs,
     Carver c;
     const size_t o_pairs = c.take<TvPair>(np), o_first = c.take<int32_t>(np + 1);
     const size_t o_obs1 = c.take<double>(2 * M), o_obs2 = c.take<double>(2 * M), o_samp = c.take<int32_t>(5 * H);
+    const bool want_lo = lo_iters > 0 || info;
+    const size_t lo_bytes = want_lo ? sizeof(double) * kTvLoDoubles * np : 0;
+    const size_t o_lo = c.take<double>(lo_bytes / sizeof(double));
     const size_t h2d = c.off;
     Carver dv = c;
     const size_t o_cand = dv.take<double>(90 * H), o_loss = dv.take<double>(10 * H), o_cnt = dv.take<int32_t>(10 * H);
@@ -131,6 +140,7 @@ extern "C" int movba_two_view(movba_handle *h, const movba_two_view_desc *descs,
     }
     std::memcpy(sg + o_pairs, pairs.data(), sizeof(TvPair) * np);
     std::memcpy(sg + o_first, hyp_first.data(), sizeof(int32_t) * (np + 1));
+    if (want_lo) std::memset(sg + o_lo, 0, lo_bytes);
 
     TvDev t{};
     t.n_pairs = n; t.n_hyp_total = (int32_t)H;
@@ -141,9 +151,12 @@ extern "C" int movba_two_view(movba_handle *h, const movba_two_view_desc *descs,
     t.cnt = reinterpret_cast<int32_t *>(ar + o_cnt); t.nsol = reinterpret_cast<int32_t *>(ar + o_nsol);
     t.inl0 = reinterpret_cast<uint8_t *>(ar + o_inl0); t.cosv = reinterpret_cast<double *>(ar + o_cos);
     t.rec = reinterpret_cast<double *>(ar + o_rec);
+    t.lo = want_lo ? reinterpret_cast<double *>(ar + o_lo) : nullptr;
+    t.lo_iters = lo_iters;
 
     HIP_TRY(hipMemcpyAsync(ar, sg, h2d, hipMemcpyHostToDevice, h->stream));
     HIP_TRY(launch_two_view(t, h->stream));
+    if (want_lo) HIP_TRY(hipMemcpyAsync(sg + o_lo, ar + o_lo, lo_bytes, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
 
     for (int k = 0; k < n; ++k) {
@@ -160,6 +173,14 @@ extern "C" int movba_two_view(movba_handle *h, const movba_two_view_desc *descs,
         for (int e = 0; e < 9; ++e) r.E[e] = o[7 + e];
         r.parallax_deg = o[16]; r.outcome = (int32_t)o[17]; r.n_inliers = (int32_t)o[18]; r.n_pass = (int32_t)o[19];
         r.n_good = (int32_t)o[20]; r.samples_used = (int32_t)o[21];
+        if (info) {
+            // (a slot no kernel wrote - no winner, fewer than 5 matches - is still the zeros that went up)
+            const double *l = reinterpret_cast<const double *>(sg + o_lo) + (size_t)kTvLoDoubles * k;
+            movba_two_view_lo_info &fo = info[k];
+            fo.loss0 = l[18]; fo.loss = l[19];
+            for (int e = 0; e < 9; ++e) fo.E0[e] = l[9 + e];
+            fo.kept = (int32_t)l[20]; fo.steps = (int32_t)l[21]; fo.n_inliers0 = (int32_t)l[22]; fo.pad = 0;
+        }
         if (m) {
             const size_t nh = (size_t)p.n_hyp, h0 = (size_t)p.h0;
             if (r.hyp_nsol) HIP_TRY(hipMemcpy(r.hyp_nsol, ar + o_nsol + sizeof(int32_t) * h0, sizeof(int32_t) * nh, hipMemcpyDeviceToHost));
@@ -169,4 +190,17 @@ extern "C" int movba_two_view(movba_handle *h, const movba_two_view_desc *descs,
     }
     for (int k = 0; k < n; ++k) results[k].status = pairs[k].n ? MOVBA_OK : MOVBA_EMPTY;
     return MOVBA_OK;
+}
+
+}  // namespace
+
+extern "C" int movba_two_view(movba_handle *h, const movba_two_view_desc *descs, movba_two_view_result *results, int32_t n)
+{
+    return two_view_front(h, descs, results, n, 0, nullptr);
+}
+
+extern "C" int movba_two_view_lo(movba_handle *h, const movba_two_view_desc *descs, movba_two_view_result *results, int32_t n,
+                                 int32_t lo_iters, movba_two_view_lo_info *info)
+{
+    return two_view_front(h, descs, results, n, lo_iters, info);
 }

@@ -1,4 +1,4 @@
-// Device view + launch wrapper of movba_two_view (two_view.hip; host side: two_view.cpp).
+// Device view + launch wrapper of movba_two_view and movba_two_view_lo (two_view.hip; host side: two_view.cpp).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -32,12 +32,16 @@ struct TvDev {
     uint8_t *inl0;                  // all matches
     double *cosv;                   // all matches
     double *rec;                    // n_pairs x kTvRecDoubles
+    // movba_two_view_lo: n_pairs x kTvLoDoubles (two_view_math.h), zero-filled by the host and part of its upload; nullptr when
+    // neither a refit nor `info` is asked for.  A slot whose mark is set holds the refit's kept E: k_tv_recover goes on with it
+    double *lo;
+    int32_t lo_iters;               // steps of the refit at most; 0: k_tv_lo is not launched
 };
 
 constexpr int kTvThreads = 256;
 constexpr int kTvRecDoubles = 32;   // winner E 9, R 9, t 3, n_inliers, n_pass, samples_used, winner index, has_model
 
-// k_tv_hyp, k_tv_recover, k_tv_check on the stream, in that order
+// k_tv_hyp, k_tv_lo (lo_iters > 0 only), k_tv_recover, k_tv_check on the stream, in that order
 hipError_t launch_two_view(const TvDev &d, hipStream_t s);
 
 }  // namespace movba

@@ -1,10 +1,17 @@
-// The three kernels of movba_two_view (include/movba.h); the arithmetic is two_view_math.h.
+// The kernels of movba_two_view and movba_two_view_lo (include/movba.h); the arithmetic is two_view_math.h.
 //   k_tv_hyp      one workgroup per (pair, sample), found by binary search over the prefix of the pairs' sample counts (as
 //                 k_pose_hyp_b finds its frame).  The five-point solve runs over the whole workgroup with its tables in LDS
 //                 (tv_five_point: the lanes own the columns of the 10 x 20 elimination, the intervals of the root search and
 //                 the roots); then the four waves score the candidates over the pair's matches.
-//   k_tv_recover  one workgroup per pair: best candidate per sample (one thread per sample), the stopping rule's walk, the
-//                 threshold mask, the decomposition of E, the four cheirality counts (one wave each), the final mask.
+//   k_tv_lo       (movba_two_view_lo with lo_iters > 0 only) one workgroup per pair: the winner as k_tv_recover finds it
+//                 (tv_select), then lo_iters + 1 passes over the pair's matches - threads stride the matches with the 21
+//                 accumulators in registers, a butterfly per wave, the four waves combined in LDS in wave order - between
+//                 which thread 0 factors the 5 x 5 system, steps and rebuilds E and its derivatives in LDS.  The kept E and
+//                 the call's `info` go to the pair's slot of TvDev::lo.  The matches are read from global memory in every
+//                 pass: a pair of MOVBA_MAX_TWO_VIEW_MATCHES matches is 1 MiB of coordinates, several times the LDS.
+//   k_tv_recover  one workgroup per pair: best candidate per sample (one thread per sample), the stopping rule's walk
+//                 (tv_select) - or the kept E of a marked slot -, the threshold mask, the decomposition of E, the four
+//                 cheirality counts (one wave each), the final mask.
 //   k_tv_check    one workgroup per pair: CheckRT for every match (thread-strided), then the order statistic of the accepted
 //                 cosines by counting ranks, the outcome and the pose.
 // No atomics on floating-point data: sums are per-lane partial sums combined by a butterfly in a fixed order; counts are integers.
@@ -85,17 +92,10 @@ __global__ __launch_bounds__(kTvThreads) void k_tv_hyp(const TvDev d)
     }
 }
 
-__global__ __launch_bounds__(kTvThreads) void k_tv_recover(const TvDev d)
+// Best candidate per sample (one thread per sample), then the stopping rule's walk by thread 0: *best_s = the winner's candidate
+// index 10 h + c (< 0: none), *used_s = the samples admitted.  sl / sc / sb: LDS, MOVBA_MAX_TWO_VIEW_ITERS each.  Ends behind a barrier.
+__device__ __forceinline__ void tv_select(const TvDev &d, const TvPair &p, double *sl, int *sc, int *sb, int *best_s, int *used_s, int tid)
 {
-    __shared__ double sl[MOVBA_MAX_TWO_VIEW_ITERS];
-    __shared__ int sc[MOVBA_MAX_TWO_VIEW_ITERS], sb[MOVBA_MAX_TWO_VIEW_ITERS];
-    __shared__ int best_s, used_s, n_in, cheir[4];
-    __shared__ double Rt[2][9], tt[3], Ew[9];
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const TvPair p = d.pairs[blockIdx.x];
-    double *rec = d.rec + (size_t)kTvRecDoubles * blockIdx.x;
-    const double *o1 = d.obs1 + 2 * (size_t)p.m0, *o2 = d.obs2 + 2 * (size_t)p.m0;
-    uint8_t *inl0 = d.inl0 + p.m0;
     for (int h = tid; h < p.n_hyp; h += kTvThreads) {
         const size_t hg = (size_t)p.h0 + h;
         const int ns = d.nsol[hg];
@@ -107,22 +107,118 @@ __global__ __launch_bounds__(kTvThreads) void k_tv_recover(const TvDev d)
         }
         sl[h] = bl; sc[h] = bc; sb[h] = bi;
     }
-    if (tid == 0) { n_in = 0; cheir[0] = cheir[1] = cheir[2] = cheir[3] = 0; }
     __syncthreads();
     if (tid == 0) {
         int b, u;
         tv_walk(sl, sc, sb, p.n_hyp, p.n, p.conf, &b, &u);
-        best_s = b; used_s = u;
+        *best_s = b; *used_s = u;
     }
     __syncthreads();
+}
+
+// One pass of the refit over the pair's matches at E (and, for a pass that takes a step, its five derivatives dE), both in LDS:
+// thread-strided with the kTvLoAcc accumulators in registers, a butterfly per wave, then thread a adds the four waves' sums of
+// accumulator a in wave order.  acc (LDS) holds the sums behind the closing barrier; cnt4 (nullptr: not counted) the waves'
+// numbers of matches within the threshold by k_tv_recover's own test.
+__device__ __forceinline__ void tv_lo_pass(const TvPair &p, const double *o1, const double *o2, const double *E, const double (*dE)[9], bool want,
+                                           const Magsac &ms, double (*red)[kTvLoAcc], double *acc, int *cnt4, int tid)
+{
+    const int lane = tid & 63, wv = tid >> 6;
+    const double inv_f = 1.0 / p.f, f2 = p.f * p.f;
+    double Ec[9], dEc[5][9], a[kTvLoAcc];
+#pragma unroll
+    for (int e = 0; e < 9; ++e) Ec[e] = E[e];
+#pragma unroll
+    for (int j = 0; j < 5; ++j)
+#pragma unroll
+        for (int e = 0; e < 9; ++e) dEc[j][e] = want ? dE[j][e] : 0.0;
+#pragma unroll
+    for (int e = 0; e < kTvLoAcc; ++e) a[e] = 0.0;
+    int cn = 0;
+    for (int i = tid; i < p.n; i += kTvThreads) {
+        const double2 u = reinterpret_cast<const double2 *>(o1)[i], v = reinterpret_cast<const double2 *>(o2)[i];
+        const double x1 = (u.x - p.cx) * inv_f, y1 = (u.y - p.cy) * inv_f, x2 = (v.x - p.cx) * inv_f, y2 = (v.y - p.cy) * inv_f;
+        tv_lo_accumulate(ms, p.thr2, Ec, dEc, want, p.f, x1, y1, x2, y2, a);
+        if (cnt4) cn += f2 * tv_sampson2(Ec, x1, y1, x2, y2) <= p.thr2 ? 1 : 0;
+    }
+#pragma unroll
+    for (int e = 0; e < kTvLoAcc; ++e) {
+        double v = a[e];
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
+        if (lane == 0) red[wv][e] = v;
+    }
+    if (cnt4) {
+        cn = wave_sum(cn);
+        if (lane == 0) cnt4[wv] = cn;
+    }
+    __syncthreads();
+    if (tid < kTvLoAcc) acc[tid] = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
+    __syncthreads();
+}
+
+__global__ __launch_bounds__(kTvThreads) void k_tv_lo(const TvDev d)
+{
+    __shared__ double sl[MOVBA_MAX_TWO_VIEW_ITERS];
+    __shared__ int sc[MOVBA_MAX_TWO_VIEW_ITERS], sb[MOVBA_MAX_TWO_VIEW_ITERS];
+    __shared__ int best_s, used_s, go_s, cnt4[kTvThreads / 64];
+    __shared__ TvLoState st;
+    __shared__ TvLoTrack trk;           // (thread 0's)
+    __shared__ double red[kTvThreads / 64][kTvLoAcc], acc[kTvLoAcc];
+    const int tid = threadIdx.x;
+    const TvPair p = d.pairs[blockIdx.x];
+    if (p.n_hyp <= 0) return;
+    tv_select(d, p, sl, sc, sb, &best_s, &used_s, tid);
+    const int best = best_s;
+    if (best < 0) return;               // (the slot stays zero: k_tv_recover finds no winner either)
+    const double *o1 = d.obs1 + 2 * (size_t)p.m0, *o2 = d.obs2 + 2 * (size_t)p.m0;
+    const Magsac ms(p.thr2);
+    if (tid == 0) tv_lo_begin(d.cand + 90 * (size_t)p.h0 + 9 * (size_t)best, st, trk);
+    __syncthreads();
+    for (int k = 0; k <= d.lo_iters; ++k) {
+        tv_lo_pass(p, o1, o2, st.E, st.dE, k < d.lo_iters, ms, red, acc, k == 0 ? cnt4 : nullptr, tid);
+        if (tid == 0) go_s = tv_lo_advance(st, trk, acc, k, d.lo_iters) ? 1 : 0;
+        __syncthreads();
+        if (!go_s) break;
+    }
+    if (tid == 0) {
+        double *slot = d.lo + (size_t)kTvLoDoubles * blockIdx.x;
+        tv_lo_result(trk, slot);
+#pragma unroll
+        for (int e = 0; e < 9; ++e) slot[9 + e] = trk.E0[e];
+        slot[18] = trk.loss0; slot[19] = trk.loss; slot[20] = (double)trk.kept; slot[21] = (double)trk.steps;
+        slot[22] = (double)(((cnt4[0] + cnt4[1]) + cnt4[2]) + cnt4[3]);
+        slot[23] = 1.0;
+    }
+}
+
+__global__ __launch_bounds__(kTvThreads) void k_tv_recover(const TvDev d)
+{
+    __shared__ double sl[MOVBA_MAX_TWO_VIEW_ITERS];
+    __shared__ int sc[MOVBA_MAX_TWO_VIEW_ITERS], sb[MOVBA_MAX_TWO_VIEW_ITERS];
+    __shared__ int best_s, used_s, n_in, cheir[4];
+    __shared__ double Rt[2][9], tt[3], Ew[9];
+    __shared__ double red[kTvThreads / 64][kTvLoAcc], acc[kTvLoAcc];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const TvPair p = d.pairs[blockIdx.x];
+    double *rec = d.rec + (size_t)kTvRecDoubles * blockIdx.x;
+    const double *o1 = d.obs1 + 2 * (size_t)p.m0, *o2 = d.obs2 + 2 * (size_t)p.m0;
+    uint8_t *inl0 = d.inl0 + p.m0;
+    if (tid == 0) { n_in = 0; cheir[0] = cheir[1] = cheir[2] = cheir[3] = 0; }
+    tv_select(d, p, sl, sc, sb, &best_s, &used_s, tid);
     const int best = best_s;
     if (best < 0) {
         for (int i = tid; i < p.n; i += kTvThreads) { inl0[i] = 0; p.inlier[i] = 0; }
         if (tid < kTvRecDoubles) rec[tid] = tid == 23 ? (double)used_s : 0.0;
         return;
     }
-    if (tid < 9) Ew[tid] = d.cand[90 * (size_t)p.h0 + 9 * (size_t)best + tid];
+    // the refit's kept E where k_tv_lo has marked the pair's slot, else the winner itself
+    double *slot = d.lo ? d.lo + (size_t)kTvLoDoubles * blockIdx.x : nullptr;
+    const bool refit = slot && slot[23] != 0.0;
+    if (tid < 9) Ew[tid] = refit ? slot[tid] : d.cand[90 * (size_t)p.h0 + 9 * (size_t)best + tid];
     __syncthreads();
+    // `info` without a refit: the winner's loss by the refit's own pass
+    if (slot && !refit) tv_lo_pass(p, o1, o2, Ew, nullptr, false, Magsac(p.thr2), red, acc, nullptr, tid);
     const double inv_f = 1.0 / p.f, f2 = p.f * p.f;
     double Ec[9];
 #pragma unroll
@@ -177,6 +273,13 @@ __global__ __launch_bounds__(kTvThreads) void k_tv_recover(const TvDev d)
         rec[21] = (double)n_in; rec[22] = (double)cheir[pick]; rec[23] = (double)used_s; rec[24] = (double)best;
         rec[25] = n_in > 0 ? 1.0 : 0.0;
         for (int e = 26; e < kTvRecDoubles; ++e) rec[e] = 0.0;
+        if (slot && !refit) {
+#pragma unroll
+            for (int e = 0; e < 9; ++e) slot[9 + e] = Ec[e];
+            slot[18] = acc[20]; slot[19] = acc[20]; slot[22] = (double)n_in;
+        }
+        if (slot && n_in == 0)          // (MOVBA_TV_NO_MODEL: a zeroed `info`)
+            for (int e = 0; e < kTvLoDoubles - 1; ++e) slot[e] = 0.0;
     }
 }
 
@@ -268,6 +371,7 @@ hipError_t launch_two_view(const TvDev &d, hipStream_t s)
 {
     if (d.n_pairs <= 0) return hipGetLastError();
     if (d.n_hyp_total > 0) hipLaunchKernelGGL(k_tv_hyp, dim3(d.n_hyp_total), dim3(kTvThreads), 0, s, d);
+    if (d.n_hyp_total > 0 && d.lo && d.lo_iters > 0) hipLaunchKernelGGL(k_tv_lo, dim3(d.n_pairs), dim3(kTvThreads), 0, s, d);
     hipLaunchKernelGGL(k_tv_recover, dim3(d.n_pairs), dim3(kTvThreads), 0, s, d);
     hipLaunchKernelGGL(k_tv_check, dim3(d.n_pairs), dim3(kTvThreads), 0, s, d);
     return hipGetLastError();

@@ -1,7 +1,8 @@
 // The arithmetic of movba_two_view (include/movba.h): the five-point minimal solver, the Sampson score, the decomposition of
-// an essential matrix with its cheirality test, and the body of TwoViewReconstruction::CheckRT
-// (TwoViewReconstruction.cc:120-245) for one match.  Plain C++ over doubles, shared by the kernels (two_view.hip) and by the
-// host-only test build's fake device (tests/hipstub/fake_two_view.cpp).
+// an essential matrix with its cheirality test, the local optimisation of movba_two_view_lo (tv_lo_*), and the body of
+// TwoViewReconstruction::CheckRT (TwoViewReconstruction.cc:120-245) for one match.  Plain C++ over doubles, shared by the
+// kernels (two_view.hip), by the host-only test build's fake device (tests/hipstub/fake_two_view.cpp) and by the serial
+// driver of the refit (tests/two_view_lo/lo_main.cpp).
 //
 // The solver (tv_five_point) is written for a GROUP of `nl` co-operating lanes that share one TvWork (LDS on the device) and
 // meet at `sync()`; every loop over independent items is strided by the lane, so the same text runs on one host thread
@@ -546,6 +547,219 @@ __host__ __device__ __forceinline__ uint8_t tv_check(const double *R, const doub
     X[0] = P0; X[1] = P1; X[2] = P2;
     *cosp = cosv;
     return cosv < kTvCosGood ? MOVBA_TV_CHK_GOOD : MOVBA_TV_CHK_LOW_PARALLAX;
+}
+
+// ---- stage 2b: local optimisation of the winner (movba_two_view_lo, include/movba.h) ----
+// Iteratively reweighted Gauss-Newton on the signed Sampson distance with sigma-consensus++ weights over E = [t]x R, |t| = 1.
+constexpr int kTvLoAcc = 21;        // per pass: the 15 entries of H's upper triangle (row-major), g 5, the loss
+constexpr int kTvLoDoubles = 24;    // per-pair slot: kept E 9, E0 9, loss0, loss, kept, steps, n_inliers0, mark
+
+struct TvLoState {
+    double R[9], t[3];
+    double E[9];            // what the pass scores: E0 itself at iterate 0, [t]x R afterwards
+    double dE[5][9];        // dE / d omega_k = [t]x [e_k]x R, dE / d tau_j = [b_j]x R
+};
+
+// out = [v]x M (row-major 3 x 3)
+__host__ __device__ __forceinline__ void tv_skew_mul(const double *v, const double *M, double *out)
+{
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        out[c] = v[1] * M[6 + c] - v[2] * M[3 + c];
+        out[3 + c] = v[2] * M[c] - v[0] * M[6 + c];
+        out[6 + c] = v[0] * M[3 + c] - v[1] * M[c];
+    }
+}
+
+// the tangent basis of the unit vector t: b1 = normalise(t x e_k), k the index of the smallest |t_k| (the lowest on a tie), b2 = t x b1
+__host__ __device__ inline void tv_lo_tangent(const double *t, double *b1, double *b2)
+{
+    int k = 0;
+    if (fabs(t[1]) < fabs(t[k])) k = 1;
+    if (fabs(t[2]) < fabs(t[k])) k = 2;
+    const double e[3] = { k == 0 ? 1.0 : 0.0, k == 1 ? 1.0 : 0.0, k == 2 ? 1.0 : 0.0 };
+    b1[0] = t[1] * e[2] - t[2] * e[1]; b1[1] = t[2] * e[0] - t[0] * e[2]; b1[2] = t[0] * e[1] - t[1] * e[0];
+    const double inv = 1.0 / sqrt(b1[0] * b1[0] + b1[1] * b1[1] + b1[2] * b1[2]);
+    b1[0] *= inv; b1[1] *= inv; b1[2] *= inv;
+    b2[0] = t[1] * b1[2] - t[2] * b1[1]; b2[1] = t[2] * b1[0] - t[0] * b1[2]; b2[2] = t[0] * b1[1] - t[1] * b1[0];
+}
+
+// the five derivative matrices at (R, t)
+__host__ __device__ inline void tv_lo_derivatives(TvLoState &s)
+{
+    const double *t = s.t;
+    double b1[3], b2[3];
+    tv_lo_tangent(t, b1, b2);
+    for (int a = 0; a < 3; ++a) {
+        const double ea[3] = { a == 0 ? 1.0 : 0.0, a == 1 ? 1.0 : 0.0, a == 2 ? 1.0 : 0.0 };
+        double M[9];
+        tv_skew_mul(ea, s.R, M);
+        tv_skew_mul(t, M, s.dE[a]);
+    }
+    tv_skew_mul(b1, s.R, s.dE[3]);
+    tv_skew_mul(b2, s.R, s.dE[4]);
+}
+
+// Rule 1: (R, t) of the winner E0 - of the decomposition's two rotations the one with the larger trace, the first on equal
+// traces; t's sign so that <[t]x R, E0> >= 0.  Iterate 0 scores E0 itself.
+__host__ __device__ inline void tv_lo_start(const double *E0, TvLoState &s)
+{
+    double R1[9], R2[9], E[9];
+    tv_decompose(E0, R1, R2, s.t);
+    const bool second = R2[0] + R2[4] + R2[8] > R1[0] + R1[4] + R1[8];
+    for (int e = 0; e < 9; ++e) s.R[e] = second ? R2[e] : R1[e];
+    tv_skew_mul(s.t, s.R, E);
+    double dot = 0.0;
+    for (int e = 0; e < 9; ++e) dot += E[e] * E0[e];
+    if (dot < 0.0) { s.t[0] = -s.t[0]; s.t[1] = -s.t[1]; s.t[2] = -s.t[2]; }
+    for (int e = 0; e < 9; ++e) s.E[e] = E0[e];
+    tv_lo_derivatives(s);
+}
+
+// Rule 3 for one match (normalised coordinates): the signed Sampson distance in pixels and, for a pass that takes a step, its
+// exact derivative by the five parameters (the denominator's included)
+__host__ __device__ __forceinline__ double tv_lo_residual(const double *E, const double (*dE)[9], bool want, double f,
+                                                          double x1, double y1, double x2, double y2, double *J)
+{
+    const double a0 = E[0] * x1 + E[1] * y1 + E[2], a1 = E[3] * x1 + E[4] * y1 + E[5], a2 = E[6] * x1 + E[7] * y1 + E[8];
+    const double b0 = E[0] * x2 + E[3] * y2 + E[6], b1 = E[1] * x2 + E[4] * y2 + E[7];
+    const double num = x2 * a0 + y2 * a1 + a2, den = a0 * a0 + a1 * a1 + b0 * b0 + b1 * b1;
+    const double is = 1.0 / sqrt(den);
+    if (want) {
+        const double hn = 0.5 * num / den;
+#pragma unroll
+        for (int j = 0; j < 5; ++j) {
+            const double *D = dE[j];
+            const double c0 = D[0] * x1 + D[1] * y1 + D[2], c1 = D[3] * x1 + D[4] * y1 + D[5], c2 = D[6] * x1 + D[7] * y1 + D[8];
+            const double d0 = D[0] * x2 + D[3] * y2 + D[6], d1 = D[1] * x2 + D[4] * y2 + D[7];
+            const double dnum = x2 * c0 + y2 * c1 + c2, dden = 2.0 * (a0 * c0 + a1 * c1 + b0 * d0 + b1 * d1);
+            J[j] = f * (dnum - hn * dden) * is;
+        }
+    }
+    return f * num * is;
+}
+
+// Rule 4 for one match: acc[20] += loss; with `want`, H += w J J^T (upper triangle, row-major) and g += w J r.  A match beyond
+// the gate (or with a residual that is not a number) has weight 0 and adds nothing to H and g.
+__host__ __device__ __forceinline__ void tv_lo_accumulate(const Magsac &ms, double thr2, const double *E, const double (*dE)[9], bool want,
+                                                          double f, double x1, double y1, double x2, double y2, double *acc)
+{
+    double J[5];
+    const double r = tv_lo_residual(E, dE, want, f, x1, y1, x2, y2, J);
+    double l1, wt;
+    ms.terms(r * r, true, thr2, l1, wt);
+    acc[20] += l1;
+    if (want && wt > 0.0) {
+        int e = 0;
+#pragma unroll
+        for (int i = 0; i < 5; ++i) {
+            const double wj = wt * J[i];
+#pragma unroll
+            for (int j = i; j < 5; ++j) acc[e++] += wj * J[j];
+            acc[15 + i] += wj * r;
+        }
+    }
+}
+
+// delta = -H^-1 g by Cholesky of the 5 x 5 H, no damping; false when a pivot is not positive and finite
+__host__ __device__ inline bool tv_lo_solve5(const double *acc, double *delta)
+{
+    double L[5][5];
+    int e = 0;
+    for (int i = 0; i < 5; ++i)
+        for (int j = i; j < 5; ++j) L[j][i] = acc[e++];        // (lower triangle of H)
+    for (int j = 0; j < 5; ++j) {
+        double d = L[j][j];
+        for (int k = 0; k < j; ++k) d -= L[j][k] * L[j][k];
+        if (!(d > 0.0) || !(d <= DBL_MAX)) return false;
+        const double piv = sqrt(d), ip = 1.0 / piv;
+        L[j][j] = piv;
+        for (int i = j + 1; i < 5; ++i) {
+            double v = L[i][j];
+            for (int k = 0; k < j; ++k) v -= L[i][k] * L[j][k];
+            L[i][j] = v * ip;
+        }
+    }
+    double y[5];
+    for (int i = 0; i < 5; ++i) {
+        double v = -acc[15 + i];
+        for (int k = 0; k < i; ++k) v -= L[i][k] * y[k];
+        y[i] = v / L[i][i];
+    }
+    for (int i = 4; i >= 0; --i) {
+        double v = y[i];
+        for (int k = i + 1; k < 5; ++k) v -= L[k][i] * delta[k];
+        delta[i] = v / L[i][i];
+    }
+    return true;
+}
+
+// Rule 2: R <- exp([d omega]x) R (Rodrigues), t <- normalise(t + d tau_1 b1 + d tau_2 b2); then E = [t]x R and the derivatives
+// at the new iterate.
+__host__ __device__ inline void tv_lo_update(TvLoState &s, const double *delta)
+{
+    const double wx = delta[0], wy = delta[1], wz = delta[2], th2 = wx * wx + wy * wy + wz * wz, th = sqrt(th2);
+    const double A = th2 < 1e-8 ? 1.0 - th2 / 6.0 : sin(th) / th, B = th2 < 1e-8 ? 0.5 - th2 / 24.0 : (1.0 - cos(th)) / th2;
+    const double K[9] = { 0.0, -wz, wy, wz, 0.0, -wx, -wy, wx, 0.0 };
+    double X[9], Rn[9];
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) {
+            const double k2 = K[3 * i] * K[j] + K[3 * i + 1] * K[3 + j] + K[3 * i + 2] * K[6 + j];
+            X[3 * i + j] = (i == j ? 1.0 : 0.0) + A * K[3 * i + j] + B * k2;
+        }
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) Rn[3 * i + j] = X[3 * i] * s.R[j] + X[3 * i + 1] * s.R[3 + j] + X[3 * i + 2] * s.R[6 + j];
+    for (int e = 0; e < 9; ++e) s.R[e] = Rn[e];
+    // the tangent basis at the OLD t
+    const double *t = s.t;
+    double b1[3], b2[3];
+    tv_lo_tangent(t, b1, b2);
+    double tn[3];
+    for (int i = 0; i < 3; ++i) tn[i] = t[i] + delta[3] * b1[i] + delta[4] * b2[i];
+    const double it = 1.0 / sqrt(tn[0] * tn[0] + tn[1] * tn[1] + tn[2] * tn[2]);
+    for (int i = 0; i < 3; ++i) s.t[i] = tn[i] * it;
+    tv_skew_mul(s.t, s.R, s.E);
+    tv_lo_derivatives(s);
+}
+
+// Rules 4 and 5 between the passes, for the one thread that steers the refit: the winner, the kept iterate and the lowest loss so far
+struct TvLoTrack {
+    double E0[9], Ek[9], loss0, loss;
+    int kept, steps;
+};
+
+__host__ __device__ inline void tv_lo_begin(const double *E0, TvLoState &st, TvLoTrack &tr)
+{
+    for (int e = 0; e < 9; ++e) { tr.E0[e] = E0[e]; tr.Ek[e] = E0[e]; }
+    tr.loss0 = tr.loss = 0.0; tr.kept = tr.steps = 0;
+    tv_lo_start(E0, st);
+}
+
+// after pass k (acc: its sums): keeps the iterate when its loss is the lowest so far (the lowest k wins a tie; a loss that is
+// not a number is never kept), then steps when k < lo_iters.  false: the refit ends here.
+__host__ __device__ inline bool tv_lo_advance(TvLoState &st, TvLoTrack &tr, const double *acc, int k, int lo_iters)
+{
+    const double L = acc[20];
+    if (k == 0) {
+        tr.loss0 = tr.loss = L;
+    } else if (L < tr.loss) {
+        tr.loss = L; tr.kept = k;
+        for (int e = 0; e < 9; ++e) tr.Ek[e] = st.E[e];
+    }
+    double delta[5];
+    if (k >= lo_iters || !tv_lo_solve5(acc, delta)) return false;
+    tv_lo_update(st, delta);
+    tr.steps = k + 1;
+    return true;
+}
+
+// the E handed out: E0 itself for kept = 0, else the kept [t]x R with the sign that makes <E, E0> >= 0
+__host__ __device__ inline void tv_lo_result(const TvLoTrack &tr, double *E)
+{
+    double dot = 0.0;
+    for (int e = 0; e < 9; ++e) dot += tr.Ek[e] * tr.E0[e];
+    const double sg = dot < 0.0 ? -1.0 : 1.0;
+    for (int e = 0; e < 9; ++e) E[e] = tr.kept ? sg * tr.Ek[e] : tr.E0[e];
 }
 
 // rotation matrix (row-major) -> unit quaternion (x, y, z, w) (Eigen's conversion)

@@ -112,7 +112,13 @@ class TwoViewResult(C.Structure):
                 ("hyp_nsol", _i), ("hyp_E", _d), ("hyp_loss", _d)]
 
 
+class TwoViewLoInfo(C.Structure):
+    _fields_ = [("loss0", C.c_double), ("loss", C.c_double), ("E0", C.c_double * 9), ("kept", C.c_int32), ("steps", C.c_int32),
+                ("n_inliers0", C.c_int32), ("pad", C.c_int32)]
+
+
 MAX_TWO_VIEW_ITERS = 1024
+MAX_TWO_VIEW_LO_ITERS = 32
 MAX_TWO_VIEW_BATCH = 1024
 MAX_TWO_VIEW_MATCHES = 32768
 # movba_two_view_result::outcome (MOVBA_TV_*) and ::code (MOVBA_TV_CHK_*)
@@ -133,7 +139,7 @@ EXPORTS = ["movba_version", "movba_status_string", "movba_create", "movba_destro
            "movba_lba_export_poses_device", "movba_lba_set_pose_export", "movba_get_profile", "movba_reset_profile",
            "movba_structure_probe", "movba_pose_opt", "movba_set_profile_mask", "movba_lba_run_batch", "movba_pose_ransac_samples",
            "movba_host_alloc", "movba_host_free", "movba_dense_plan_probe", "movba_pose_opt_batch", "movba_lba_marginals", "movba_triangulate",
-           "movba_two_view", "movba_two_view_samples"]
+           "movba_two_view", "movba_two_view_samples", "movba_two_view_lo"]
 
 _libs = {False: None, True: None}
 
@@ -191,6 +197,8 @@ def lib(hooks: bool = False):
         L.movba_pose_ransac_samples.argtypes = [C.c_int32, C.c_int32, C.c_uint32, _i]
         L.movba_two_view.argtypes = [C.c_void_p, C.POINTER(TwoViewDesc), C.POINTER(TwoViewResult), C.c_int32]
         L.movba_two_view_samples.argtypes = [C.c_int32, C.c_int32, C.c_uint32, _i]
+        L.movba_two_view_lo.argtypes = [C.c_void_p, C.POINTER(TwoViewDesc), C.POINTER(TwoViewResult), C.c_int32, C.c_int32,
+                                        C.POINTER(TwoViewLoInfo)]
         L.movba_host_alloc.argtypes = [C.c_size_t]
         L.movba_host_alloc.restype = C.c_void_p
         L.movba_dense_plan_probe.argtypes = [C.c_int32, C.c_int32, C.c_int32, _i, _i, C.c_int32, _i, C.c_int32]
@@ -622,13 +630,14 @@ class Solver:
             raise MovbaError(f"movba_triangulate: {status_string(rc)}")
         return dict(points=points, code=code, n_accepted=r.n_accepted, status=rc)
 
-    def two_view(self, pairs, pinned=False, diagnostics=False) -> list:
+    def two_view(self, pairs, pinned=False, diagnostics=False, lo_iters=None) -> list:
         """movba_two_view (monocular map initialisation, TwoViewReconstruction::Reconstruct) on a list of frame pairs:
         dicts with obs1, obs2 (M, 2) pixels, cam (fx, fy, cx, cy) and optionally the keys of TWO_VIEW_DEFAULTS.  One dict per
         pair back: status (0, or 3 = MOVBA_EMPTY under 5 matches), outcome (TV_*), pose (T21), E (3, 3), parallax_deg,
         n_inliers, n_pass, n_good, samples_used, inlier, points, good, code (TV_CHK_*) per match and, with diagnostics,
         hyp_nsol, hyp_E, hyp_loss.  pinned: per-match arrays in movba_host_alloc memory (written by the kernels; they live
-        until close())."""
+        until close()).  lo_iters: None calls movba_two_view; an integer calls movba_two_view_lo (local optimisation of the
+        winner with that many steps at most) and adds lo_kept, lo_steps, loss0, loss, n_inliers0 and E0 (3, 3) to every dict."""
         n = len(pairs)
         descs = (TwoViewDesc * max(n, 1))(); res = (TwoViewResult * max(n, 1))()
         keeps = []
@@ -636,9 +645,13 @@ class Solver:
             d, r, keep = two_view_desc(pair, self._pinned if pinned else np.zeros, diagnostics)
             descs[k] = d; res[k] = r
             keeps.append(keep)
-        rc = self._L.movba_two_view(self._h, descs, res, n)
+        if lo_iters is None:
+            rc = self._L.movba_two_view(self._h, descs, res, n)
+        else:
+            info = (TwoViewLoInfo * max(n, 1))()
+            rc = self._L.movba_two_view_lo(self._h, descs, res, n, int(lo_iters), info)
         if rc < 0:
-            raise MovbaError(f"movba_two_view: {status_string(rc)}")
+            raise MovbaError(f"movba_two_view{'' if lo_iters is None else '_lo'}: {status_string(rc)}")
         out = []
         for k in range(n):
             r, keep = res[k], keeps[k]
@@ -646,5 +659,9 @@ class Solver:
                      parallax_deg=r.parallax_deg, n_inliers=r.n_inliers, n_pass=r.n_pass, n_good=r.n_good,
                      samples_used=r.samples_used)
             o.update({key: keep[key] for key in ("inlier", "points", "good", "code", "hyp_nsol", "hyp_E", "hyp_loss") if key in keep})
+            if lo_iters is not None:
+                fo = info[k]
+                o.update(lo_kept=fo.kept, lo_steps=fo.steps, loss0=fo.loss0, loss=fo.loss, n_inliers0=fo.n_inliers0,
+                         E0=np.array(fo.E0[:]).reshape(3, 3))
             out.append(o)
         return out
