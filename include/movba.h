@@ -544,6 +544,104 @@ typedef struct {
 int  movba_two_view_lo(movba_handle *h, const movba_two_view_desc *descs, movba_two_view_result *results, int32_t n,
                        int32_t lo_iters, movba_two_view_lo_info *info /* n, or NULL */);
 
+/* The second half of the monocular start: the numeric body of Tracking::CreateInitialMapMonocular (Tracking.cc:641-748) behind
+ * movba_two_view / movba_two_view_lo, for n independent frame pairs per call - Optimizer::GlobalBundleAdjustemnt(map, 20) over
+ * the two keyframes (:688, Optimizer.cc:68-395), ComputeSceneMedianDepth(2) of the first (:690, KeyFrame.cc:757-791), the
+ * acceptance test (:694) and the rescaling of the baseline and of every point to median depth 1 (:702-717).  Building the
+ * KeyFrame / MapPoint objects stays with the caller. */
+typedef struct {
+    int32_t n_matches;            /* matches of the pair, as handed to movba_two_view: 0 .. MOVBA_MAX_TWO_VIEW_MATCHES               */
+    int32_t max_iters;            /* 20 (Tracking.cc:688); 0 .. MOVBA_MAX_INIT_MAP_ITERS; 0: no optimisation, stages 3 and 4 only     */
+    int32_t max_trials;           /* g2o maxTrialsAfterFailure; 0 -> 10                                                            */
+    int32_t min_tracked;          /* 50 (Tracking.cc:694)                                                                          */
+    const double  *obs1;          /* n_matches x 2, pixels: the observation in keyframe 1                                          */
+    const double  *obs2;          /* n_matches x 2: ... in keyframe 2                                                              */
+    const double  *points;        /* n_matches x 3: mvIniP3D, in the frame of camera 1 = the world frame (Tracking.cc:631)         */
+    const uint8_t *use;           /* n_matches or NULL (all): non-zero = the match was triangulated (Tracking.cc:622-629):
+                                     movba_two_view_result::good as it is.  obs1, obs2, points, inv_sigma2_* of a match that is not
+                                     used may hold anything, NaN included: they do not reach the result                             */
+    const double  *inv_sigma2_1;  /* n_matches or NULL (= 1): mvInvLevelSigma2 of the keypoint's octave (Optimizer.cc:181-182)     */
+    const double  *inv_sigma2_2;  /* n_matches or NULL (= 1)                                                                       */
+    double pose2[7];              /* T21: qx qy qz qw tx ty tz, as movba_two_view returns it; the quaternion is normalised first   */
+    double fx, fy, cx, cy;
+    double huber_delta;           /* (double)sqrtf(5.0f) (Optimizer.cc:52, 138); <= 0: no kernel (bRobust false)                    */
+} movba_init_map_desc;
+
+#define MOVBA_MAX_INIT_MAP_ITERS 100
+
+/* outcome: what the test at Tracking.cc:694 said */
+#define MOVBA_IM_OK            0
+#define MOVBA_IM_NEG_DEPTH     1   /* medianDepth < 0                                                                              */
+#define MOVBA_IM_FEW_TRACKED   2   /* TrackedMapPoints(1) < min_tracked (= n_used: nothing was culled); also a pair without a used match */
+
+typedef struct {
+    double   pose[7];           /* T21 after the bundle adjustment; MOVBA_IM_OK: translation times 1 / median_depth (:702-704)      */
+    double  *points;            /* n_matches x 3 out: the optimised points, MOVBA_IM_OK: times 1 / median_depth (:707-717); NaN for
+                                   matches that are not used                                                                      */
+    double  *chi2;              /* n_matches x 2 out or NULL: e->chi2() of the edge in keyframe 1 and in keyframe 2 at the returned
+                                   estimate (before the rescaling, which does not change them); NaN for matches that are not used  */
+    double   median_depth;      /* ComputeSceneMedianDepth(2) of keyframe 1 after the bundle adjustment (NaN: MOVBA_EMPTY)          */
+    double   lambda;            /* final damping                                                                                  */
+    double   cost0, cost;       /* robust cost (activeRobustChi2) at the start and at the returned estimate                       */
+    int32_t  outcome;           /* MOVBA_IM_*                                                                                      */
+    int32_t  status;            /* MOVBA_OK; MOVBA_EMPTY: no used match (pose = pose2 normalised, no array written)                */
+    int32_t  n_used;            /* used matches = map points created (Tracking.cc:665-684)                                         */
+    int32_t  iters_done;        /* outer LM iterations run                                                                         */
+    int32_t  n_solves;          /* linear solves = accepted + rejected trials                                                      */
+    int32_t  last_rejected;     /* 1 if the final trial was rejected                                                               */
+    int32_t  n_chol_fail;       /* trials whose 6 x 6 factorisation met a pivot that is not positive and finite: rejected          */
+    int32_t  pad;
+} movba_init_map_result;
+
+/* the per-trial trace of one pair: movba_lba_result's n_trace / tr_* (min(n_solves, MOVBA_MAX_TRACE) entries) */
+typedef struct {
+    int32_t n_trace, pad;
+    double  tr_lambda[MOVBA_MAX_TRACE];
+    double  tr_f0[MOVBA_MAX_TRACE];
+    double  tr_f1[MOVBA_MAX_TRACE];
+    double  tr_rho[MOVBA_MAX_TRACE];
+    int32_t tr_accept[MOVBA_MAX_TRACE];
+} movba_init_map_trace;
+
+/* fp64 from the boundary to the result.  One workgroup per pair (k_init_map), the whole Levenberg-Marquardt loop inside one launch.
+ *  1. The graph (BundleAdjustment's for this map, Optimizer.cc:121-282).  Keyframe 1 fixed at the identity (Tracking gives the
+ *     initial frame the identity pose), keyframe 2 free at pose2.  One point vertex per USED match, in ascending match order,
+ *     with two monocular edges: keyframe 1 first, then keyframe 2; information inv_sigma2 I, Huber kernel with huber_delta on
+ *     every edge, all points marginalised.  There is no outlier gate: BundleAdjustment erases nothing at nLoopKF == 0.
+ *  2. The optimisation: g2o's Levenberg-Marquardt as movba_lba_solve runs it, max_iters outer iterations.
+ *     lambda0 = 1e-5 max |H_jj| over the pose block and every point block; lambda is added to the pose and the point diagonals
+ *     before the Schur complement; the reduced system - one 6 x 6 block, Hpp + lambda I - sum over the points of Hpl (Hll +
+ *     lambda I)^-1 Hpl^T with Hpl of the keyframe-2 edge - is solved by Cholesky; the points follow by back substitution; pose
+ *     update T <- exp(delta) T, point update X <- X + delta; rho = (F0 - F1) / (sum x (lambda x + b) + 1e-3); accept (rho > 0
+ *     and F1 finite): lambda *= max(1/3, min(2/3, 1 - (2 rho - 1)^3)), nu = 2; reject: lambda *= nu, nu *= 2, the estimates
+ *     are restored; up to max_trials trials per iteration while rho < 0; the run ends (Terminate) after an iteration that used
+ *     max_trials trials, met rho == 0 or a lambda that is not finite.  A failed factorisation is a rejected trial with F1 =
+ *     DBL_MAX, counted in n_chol_fail.  cost and chi2 are evaluated at the returned estimate (the oracle with
+ *     stale_error_quirk off).  Sums over the points run in a fixed tree over the workgroup: no floating-point atomics.
+ *  3. Median depth: z = third coordinate of the optimised points (camera 1 is the world frame); the median is element
+ *     (n_used - 1) / 2 of their ascending order (KeyFrame.cc:788-790 with q = 2), found exactly by counting ranks (ties by match
+ *     order; a NaN sorts by its bit pattern, above every number when positive).  The reference's depths are float.
+ *  4. Outcome, as written at Tracking.cc:694: MOVBA_IM_NEG_DEPTH when median_depth < 0, else MOVBA_IM_FEW_TRACKED when n_used <
+ *     min_tracked, else MOVBA_IM_OK.  MOVBA_IM_OK: the translation of `pose` and every point are multiplied by 1 / median_depth
+ *     (:702-714); a median of exactly 0 passes the test as it does there and gives values that are not finite.  The other
+ *     outcomes return the unscaled estimate of the bundle adjustment, so that a caller can see what was rejected.
+ *  5. The result of a pair depends on its used matches and their order alone - not on the matches that are not used, the
+ *     other pairs of the call or their order: the same pair handed over compacted (use == NULL) or spread out under a mask
+ *     gives the same bits in the used slots, and two calls give the same bits.
+ * max_iters == 0: stages 3 and 4 on the points as given, n_solves = 0, cost0 = cost = the robust cost of the input.
+ * trace: n entries or NULL; a pair with status MOVBA_EMPTY gets n_trace = 0.
+ * Conventions as movba_two_view: every descriptor is checked before anything is queued; a NULL handle, n < 0, n >
+ * MOVBA_MAX_TWO_VIEW_BATCH, NULL descs or results with n > 0, or one invalid descriptor (n_matches negative or above
+ * MOVBA_MAX_TWO_VIEW_MATCHES; obs1, obs2, points or the result's points NULL with n_matches > 0; max_iters outside 0 ..
+ * MOVBA_MAX_INIT_MAP_ITERS; max_trials or min_tracked negative; fx, fy not positive and finite; cx, cy, huber_delta or an entry
+ * of pose2 not finite; a pose2 whose quaternion is zero) gives MOVBA_ERR_ARG and nothing is written except `status`.  n == 0:
+ * MOVBA_OK.  A pair without a used match gets status MOVBA_EMPTY; the others are still solved and the call returns MOVBA_OK.
+ * One packed copy to the device, one launch, one synchronisation; `points` and `chi2` that lie in movba_host_alloc memory
+ * are written by the kernel itself.  May share a handle with an uploaded or solved window: the window, its results and later
+ * runs stay as they were. */
+int  movba_init_map(movba_handle *h, const movba_init_map_desc *descs, movba_init_map_result *results, int32_t n,
+                    movba_init_map_trace *trace /* n, or NULL */);
+
 #ifdef __cplusplus
 }
 #endif

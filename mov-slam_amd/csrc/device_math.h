@@ -1,6 +1,7 @@
 // Small fp64 device helpers shared by the HIP kernels: SE3Quat arithmetic as g2o defines it
 // (normalizeRotation, operator*, exp — SURVEY.md Appendix A.8), Eigen's quaternion <-> matrix
-// conversions, the cofactor 3x3 inverse, and fixed-order wave / block reductions.
+// conversions, the cofactor 3x3 inverse, fixed-order wave / block reductions, and the dense 6 x 6 Cholesky solve of the
+// single-workgroup LM kernels (pose_kernels.hip, init_map.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -258,5 +259,54 @@ __device__ __forceinline__ double block_reduce(double v, double *red /* NWAVES d
 
 // upper-triangle index of a symmetric 6x6, a <= b
 __device__ __forceinline__ constexpr int ut6(int a, int b) { return a * 6 - a * (a - 1) / 2 + (b - a); }
+
+// dense 6x6 LL^T solve, every thread redundantly (H upper-triangle packed 21)
+__device__ inline bool solve6(const double Hu[21], double lambda, const double b[6], double x[6])
+{
+    double L[36];
+#pragma unroll
+    for (int a = 0; a < 6; ++a)
+#pragma unroll
+        for (int c = 0; c < 6; ++c) {
+            const int i = a <= c ? a : c, j = a <= c ? c : a;
+            L[a * 6 + c] = Hu[i * 6 - i * (i - 1) / 2 + (j - i)] + (a == c ? lambda : 0.0);
+        }
+    // (every thread runs this chain by itself with one wave per SIMD: nothing hides its latency, and an fp64 division or
+    // square root is a ~30-instruction sequence of its own.  One reciprocal square root per pivot and multiplications
+    // instead of 6 square roots and 27 divisions: the chain was a third of an LM iteration)
+    bool ok = true;
+    double inv[6];
+#pragma unroll
+    for (int j = 0; j < 6; ++j) {
+        double d = L[j * 6 + j];
+#pragma unroll
+        for (int k = 0; k < j; ++k) d -= L[j * 6 + k] * L[j * 6 + k];
+        if (!(d > 0.0) || !isfinite(d)) ok = false;
+        const double r = rsqrt(d);
+        inv[j] = r;
+#pragma unroll
+        for (int i = j + 1; i < 6; ++i) {
+            double s = L[i * 6 + j];
+#pragma unroll
+            for (int k = 0; k < j; ++k) s -= L[i * 6 + k] * L[j * 6 + k];
+            L[i * 6 + j] = s * r;
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+        double s = b[i];
+#pragma unroll
+        for (int k = 0; k < i; ++k) s -= L[i * 6 + k] * x[k];
+        x[i] = s * inv[i];
+    }
+#pragma unroll
+    for (int i = 5; i >= 0; --i) {
+        double s = x[i];
+#pragma unroll
+        for (int k = i + 1; k < 6; ++k) s -= L[k * 6 + i] * x[k];
+        x[i] = s * inv[i];
+    }
+    return ok;
+}
 
 }  // namespace movba

@@ -98,54 +98,7 @@ __device__ __forceinline__ void reduce_all(double (&v)[NV], double *lds /* kRedL
     for (int k = 0; k < NV; ++k) v[k] = readlane_f64(tot, k);
 }
 
-// dense 6x6 LL^T solve, every thread redundantly (H upper-triangle packed 21)
-__device__ bool solve6(const double Hu[21], double lambda, const double b[6], double x[6])
-{
-    double L[36];
-#pragma unroll
-    for (int a = 0; a < 6; ++a)
-#pragma unroll
-        for (int c = 0; c < 6; ++c) {
-            const int i = a <= c ? a : c, j = a <= c ? c : a;
-            L[a * 6 + c] = Hu[i * 6 - i * (i - 1) / 2 + (j - i)] + (a == c ? lambda : 0.0);
-        }
-    // (every thread runs this chain by itself with one wave per SIMD: nothing hides its latency, and an fp64 division or
-    // square root is a ~30-instruction sequence of its own.  One reciprocal square root per pivot and multiplications
-    // instead of 6 square roots and 27 divisions: the chain was a third of an LM iteration)
-    bool ok = true;
-    double inv[6];
-#pragma unroll
-    for (int j = 0; j < 6; ++j) {
-        double d = L[j * 6 + j];
-#pragma unroll
-        for (int k = 0; k < j; ++k) d -= L[j * 6 + k] * L[j * 6 + k];
-        if (!(d > 0.0) || !isfinite(d)) ok = false;
-        const double r = rsqrt(d);
-        inv[j] = r;
-#pragma unroll
-        for (int i = j + 1; i < 6; ++i) {
-            double s = L[i * 6 + j];
-#pragma unroll
-            for (int k = 0; k < j; ++k) s -= L[i * 6 + k] * L[j * 6 + k];
-            L[i * 6 + j] = s * r;
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < 6; ++i) {
-        double s = b[i];
-#pragma unroll
-        for (int k = 0; k < i; ++k) s -= L[i * 6 + k] * x[k];
-        x[i] = s * inv[i];
-    }
-#pragma unroll
-    for (int i = 5; i >= 0; --i) {
-        double s = x[i];
-#pragma unroll
-        for (int k = i + 1; k < 6; ++k) s -= L[k * 6 + i] * x[k];
-        x[i] = s * inv[i];
-    }
-    return ok;
-}
+// (dense 6x6 LL^T solve: solve6 of device_math.h, shared with the two-keyframe bundle adjustment of init_map.hip)
 
 // ---------------------------------------------------------------------------------------------------------------------
 // Hypothesis stage in front of the LM: RANSAC over minimal P3P solves, so that the result does not depend on the pose the

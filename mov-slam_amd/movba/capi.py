@@ -117,6 +117,29 @@ class TwoViewLoInfo(C.Structure):
                 ("n_inliers0", C.c_int32), ("pad", C.c_int32)]
 
 
+class InitMapDesc(C.Structure):
+    _fields_ = [("n_matches", C.c_int32), ("max_iters", C.c_int32), ("max_trials", C.c_int32), ("min_tracked", C.c_int32),
+                ("obs1", _d), ("obs2", _d), ("points", _d), ("use", _u), ("inv_sigma2_1", _d), ("inv_sigma2_2", _d),
+                ("pose2", C.c_double * 7), ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double),
+                ("huber_delta", C.c_double)]
+
+
+class InitMapResult(C.Structure):
+    _fields_ = [("pose", C.c_double * 7), ("points", _d), ("chi2", _d), ("median_depth", C.c_double), ("lambda_", C.c_double),
+                ("cost0", C.c_double), ("cost", C.c_double), ("outcome", C.c_int32), ("status", C.c_int32), ("n_used", C.c_int32),
+                ("iters_done", C.c_int32), ("n_solves", C.c_int32), ("last_rejected", C.c_int32), ("n_chol_fail", C.c_int32),
+                ("pad", C.c_int32)]
+
+
+class InitMapTrace(C.Structure):
+    _fields_ = [("n_trace", C.c_int32), ("pad", C.c_int32),
+                ("tr_lambda", C.c_double * MAX_TRACE), ("tr_f0", C.c_double * MAX_TRACE), ("tr_f1", C.c_double * MAX_TRACE),
+                ("tr_rho", C.c_double * MAX_TRACE), ("tr_accept", C.c_int32 * MAX_TRACE)]
+
+
+MAX_INIT_MAP_ITERS = 100
+# movba_init_map_result::outcome (MOVBA_IM_*)
+IM_OK, IM_NEG_DEPTH, IM_FEW_TRACKED = 0, 1, 2
 MAX_TWO_VIEW_ITERS = 1024
 MAX_TWO_VIEW_LO_ITERS = 32
 MAX_TWO_VIEW_BATCH = 1024
@@ -139,7 +162,7 @@ EXPORTS = ["movba_version", "movba_status_string", "movba_create", "movba_destro
            "movba_lba_export_poses_device", "movba_lba_set_pose_export", "movba_get_profile", "movba_reset_profile",
            "movba_structure_probe", "movba_pose_opt", "movba_set_profile_mask", "movba_lba_run_batch", "movba_pose_ransac_samples",
            "movba_host_alloc", "movba_host_free", "movba_dense_plan_probe", "movba_pose_opt_batch", "movba_lba_marginals", "movba_triangulate",
-           "movba_two_view", "movba_two_view_samples", "movba_two_view_lo"]
+           "movba_two_view", "movba_two_view_samples", "movba_two_view_lo", "movba_init_map"]
 
 _libs = {False: None, True: None}
 
@@ -199,6 +222,7 @@ def lib(hooks: bool = False):
         L.movba_two_view_samples.argtypes = [C.c_int32, C.c_int32, C.c_uint32, _i]
         L.movba_two_view_lo.argtypes = [C.c_void_p, C.POINTER(TwoViewDesc), C.POINTER(TwoViewResult), C.c_int32, C.c_int32,
                                         C.POINTER(TwoViewLoInfo)]
+        L.movba_init_map.argtypes = [C.c_void_p, C.POINTER(InitMapDesc), C.POINTER(InitMapResult), C.c_int32, C.POINTER(InitMapTrace)]
         L.movba_host_alloc.argtypes = [C.c_size_t]
         L.movba_host_alloc.restype = C.c_void_p
         L.movba_dense_plan_probe.argtypes = [C.c_int32, C.c_int32, C.c_int32, _i, _i, C.c_int32, _i, C.c_int32]
@@ -367,6 +391,39 @@ def two_view_desc(pair, alloc=np.zeros, diagnostics=False):
         nh = d.ransac_iters
         keep.update(hyp_nsol=np.zeros(nh, np.int32), hyp_E=np.zeros((nh, 10, 3, 3)), hyp_loss=np.zeros((nh, 10)))
         r.hyp_nsol = _p(keep["hyp_nsol"], _i); r.hyp_E = _p(keep["hyp_E"], _d); r.hyp_loss = _p(keep["hyp_loss"], _d)
+    return d, r, keep
+
+
+INIT_MAP_DEFAULTS = dict(max_iters=20, max_trials=0, min_tracked=50, huber_delta=float(np.sqrt(np.float32(5.0))))
+
+
+def init_map_desc(pair, alloc=np.zeros, chi2=True):
+    """One frame pair - dict(obs1, obs2 (M, 2), points (M, 3), pose2 (7,), cam (fx, fy, cx, cy), optional use (M,),
+    inv_sigma2_1, inv_sigma2_2 (M,) and the keys of INIT_MAP_DEFAULTS) -> (movba_init_map_desc, movba_init_map_result with its
+    output arrays, the arrays both point into)."""
+    keep = dict(obs1=np.ascontiguousarray(pair["obs1"], np.float64).reshape(-1, 2),
+                obs2=np.ascontiguousarray(pair["obs2"], np.float64).reshape(-1, 2),
+                points_in=np.ascontiguousarray(pair["points"], np.float64).reshape(-1, 3))
+    m = len(keep["obs1"])
+    d = InitMapDesc()
+    d.n_matches = m; d.obs1 = _p(keep["obs1"], _d); d.obs2 = _p(keep["obs2"], _d); d.points = _p(keep["points_in"], _d)
+    if pair.get("use") is not None:
+        keep["use"] = np.ascontiguousarray(pair["use"], np.uint8)
+        d.use = _p(keep["use"], _u)
+    for key in ("inv_sigma2_1", "inv_sigma2_2"):
+        if pair.get(key) is not None:
+            keep[key] = np.ascontiguousarray(pair[key], np.float64)
+            setattr(d, key, _p(keep[key], _d))
+    d.pose2 = (C.c_double * 7)(*[float(v) for v in pair["pose2"]])
+    d.fx, d.fy, d.cx, d.cy = pair["cam"]
+    for key, val in INIT_MAP_DEFAULTS.items():
+        setattr(d, key, pair.get(key, val))
+    keep["points"] = alloc((m, 3), np.float64)
+    r = InitMapResult()
+    r.points = _p(keep["points"], _d)
+    if chi2:
+        keep["chi2"] = alloc((m, 2), np.float64)
+        r.chi2 = _p(keep["chi2"], _d)
     return d, r, keep
 
 
@@ -663,5 +720,36 @@ class Solver:
                 fo = info[k]
                 o.update(lo_kept=fo.kept, lo_steps=fo.steps, loss0=fo.loss0, loss=fo.loss, n_inliers0=fo.n_inliers0,
                          E0=np.array(fo.E0[:]).reshape(3, 3))
+            out.append(o)
+        return out
+
+    def init_map(self, pairs, pinned=False, trace=False) -> list:
+        """movba_init_map (the two-keyframe bundle adjustment, median depth and rescaling of
+        Tracking::CreateInitialMapMonocular) on a list of frame pairs: dicts as init_map_desc takes them - movba_two_view's
+        pose, points and good go in as pose2, points and use.  One dict per pair back: status (0, or 3 = MOVBA_EMPTY without
+        a used match), outcome (IM_*), pose (T21), points (M, 3), chi2 (M, 2), median_depth, n_used, iters_done, n_solves,
+        last_rejected, n_chol_fail, lam, cost0, cost and, with trace, trace = dict(lam, f0, f1, rho, accept).  pinned:
+        per-match arrays in movba_host_alloc memory (written by the kernel; they live until close())."""
+        n = len(pairs)
+        descs = (InitMapDesc * max(n, 1))(); res = (InitMapResult * max(n, 1))()
+        tr = (InitMapTrace * max(n, 1))() if trace else None
+        keeps = []
+        for k, pair in enumerate(pairs):
+            d, r, keep = init_map_desc(pair, self._pinned if pinned else np.zeros)
+            descs[k] = d; res[k] = r
+            keeps.append(keep)
+        rc = self._L.movba_init_map(self._h, descs, res, n, tr)
+        if rc < 0:
+            raise MovbaError(f"movba_init_map: {status_string(rc)}")
+        out = []
+        for k in range(n):
+            r, keep = res[k], keeps[k]
+            o = dict(status=r.status, outcome=r.outcome, pose=np.array(r.pose[:]), points=keep["points"], chi2=keep["chi2"],
+                     median_depth=r.median_depth, n_used=r.n_used, iters_done=r.iters_done, n_solves=r.n_solves,
+                     last_rejected=r.last_rejected, n_chol_fail=r.n_chol_fail, lam=r.lambda_, cost0=r.cost0, cost=r.cost)
+            if trace:
+                t, nt = tr[k], tr[k].n_trace
+                o["trace"] = dict(lam=np.array(t.tr_lambda[:nt]), f0=np.array(t.tr_f0[:nt]), f1=np.array(t.tr_f1[:nt]),
+                                  rho=np.array(t.tr_rho[:nt]), accept=np.array(t.tr_accept[:nt]))
             out.append(o)
         return out
