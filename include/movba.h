@@ -642,6 +642,106 @@ typedef struct {
 int  movba_init_map(movba_handle *h, const movba_init_map_desc *descs, movba_init_map_result *results, int32_t n,
                     movba_init_map_trace *trace /* n, or NULL */);
 
+/* The per-point visibility arithmetic between the poses this library returns and the next set of matches it is given (matching
+ * in this fork is by track id, not by descriptor), for many frames and keyframes per call: Frame::isInFrustum over the local
+ * map points of a tracked frame (Frame.cc:456-519, from Tracking::SearchLocalPoints, Tracking.cc:1134-1152), the gates at the
+ * head of MOVMatcher::Fuse (MOVMatcher.h:207-245, from LocalMapping::SearchInNeighbors, LocalMapping.cc:558, :586) and
+ * KeyFrame::ComputeSceneMedianDepth (KeyFrame.cc:757-791), which feeds the baseline test in front of triangulation
+ * (LocalMapping.cc:268-287).  A view is one frame or keyframe with one list of map points in one mode; a keyframe that needs
+ * two lists appears as two views.  The mnLastFrameSeen and isBad filters, IncreaseVisible, the track-id lookup, Replace and
+ * AddObservation, the far-points test on track_depth and the division baseline / median_depth stay with the caller. */
+#define MOVBA_VIEW_FRUSTUM 0   /* Frame.cc:464-518, the monocular branch (this fork's frames have Nleft == -1)          */
+#define MOVBA_VIEW_FUSE    1   /* MOVMatcher.h:207-245                                                                  */
+#define MOVBA_VIEW_DEPTH   2   /* KeyFrame.cc:775-790: z only, then the median                                          */
+#define MOVBA_MAX_VIEW_BATCH 4096
+
+typedef struct {
+    /* the point table, shared by all views */
+    int32_t n_points;
+    int32_t n_views;
+    const double  *points;          /* n_points x 3, world (MapPoint::GetWorldPos)                                         */
+    const double  *normals;         /* n_points x 3 (MapPoint::GetNormal); may be NULL when every view is a DEPTH view      */
+    const double  *max_distance;    /* n_points: the raw mfMaxDistance - the 1.2 of GetMaxDistanceInvariance is applied here;
+                                       NULL as normals                                                                     */
+    const double  *min_distance;    /* n_points: the raw mfMinDistance (0.8 applied here); NULL as normals                 */
+    /* views: every array has one entry per view */
+    const int32_t *mode;            /* MOVBA_VIEW_*                                                                        */
+    const double  *poses;           /* x 7: qx qy qz qw tx ty tz = Tcw, as movba_lba_desc::poses; the quaternion is normalised
+                                       before use; the camera centre is Ow = -Rcw^T tcw, computed from the pose            */
+    const double  *cam;             /* x 4: fx fy cx cy (pinhole)                                                          */
+    const double  *bf;              /* x 1, or NULL: 0 (Frame::mbf, :512)                                                  */
+    const double  *bounds;          /* x 4: mnMinX mnMaxX mnMinY mnMaxY; NULL when every view is a DEPTH view              */
+    const double  *log_scale_factor;/* x 1: mfLogScaleFactor (MapPoint::PredictScale); NULL without a FRUSTUM view         */
+    const int32_t *n_levels;        /* x 1: mnScaleLevels; NULL without a FRUSTUM view                                     */
+    const double  *cos_limit;       /* x 1: viewingCosLimit, 0.5 at Tracking.cc:1143; NULL without a FRUSTUM view.  FUSE
+                                       views use the reference's literal 0.5 * dist3D and ignore it                        */
+    const int32_t *q;               /* x 1: the divisor of ComputeSceneMedianDepth, 2 at both call sites; NULL without a
+                                       DEPTH view                                                                          */
+    /* items: n_items = view_ptr[n_views], those of view v are [view_ptr[v], view_ptr[v + 1]) */
+    const int32_t *view_ptr;        /* n_views + 1: ascending prefix, view_ptr[0] = 0                                      */
+    const int32_t *item_point;      /* n_items: indices into the point table                                               */
+} movba_view_desc;      /* 128 bytes */
+
+/* code[i]: what happened to item i, in the order the reference tests it (each reject is one of its returns / `continue`s) */
+#define MOVBA_VP_VISIBLE         1   /* FRUSTUM: isInFrustum returned true (:518)                                         */
+#define MOVBA_VP_FUSE_CANDIDATE  2   /* FUSE: every gate in front of the keypoint loop passed (MOVMatcher.h:245)           */
+#define MOVBA_VP_DEPTH_ITEM      3   /* DEPTH: the item's z is in the view's list                                          */
+#define MOVBA_VP_REJ_BEHIND     16   /* z < 0 (Frame.cc:474, MOVMatcher.h:211)                                             */
+#define MOVBA_VP_REJ_U          17   /* FRUSTUM: u < minX || u > maxX (:479)                                               */
+#define MOVBA_VP_REJ_V          18   /* FRUSTUM: v < minY || v > maxY (:481)                                               */
+#define MOVBA_VP_REJ_IMAGE      19   /* FUSE: !(u >= minX && u < maxX && v >= minY && v < maxY) (KeyFrame.cc:735)          */
+#define MOVBA_VP_REJ_DIST       20   /* dist < 0.8 min_distance || dist > 1.2 max_distance (Frame.cc:493, MOVMatcher.h:231) */
+#define MOVBA_VP_REJ_ANGLE      21   /* FRUSTUM: PO.Pn / dist < cos_limit (:501); FUSE: PO.Pn < 0.5 dist (:240)            */
+
+typedef struct {
+    uint8_t *code;              /* n_items out: MOVBA_VP_* (required when n_items > 0)                                     */
+    /* per item, each NULL or n_items entries; NaN (level: -1) where the reference had not computed the value when it returned */
+    double  *z;                 /* third camera coordinate: every item of every mode                                       */
+    double  *uv;                /* x 2, the pinhole projection: FRUSTUM and FUSE items from the depth test passed on        */
+    double  *dist;              /* |P - Ow|: FRUSTUM and FUSE items from the bounds passed on                              */
+    double  *view_cos;          /* PO.Pn / dist: FRUSTUM items from the distance gate passed on                            */
+    int32_t *level;             /* nPredictedLevel: accepted FRUSTUM items                                                 */
+    double  *ur;                /* u - bf / z (mTrackProjXR): accepted FRUSTUM items                                       */
+    double  *track_depth;       /* |Pc| (mTrackDepth): accepted FRUSTUM items                                              */
+    /* per view (required when n_views > 0) */
+    int32_t *n_accepted;        /* n_views out: items with an accepted code - FRUSTUM: the reference's nToMatch (Tracking.cc:1146),
+                                   FUSE: the candidates, DEPTH: the length of the list                                     */
+    double  *median_depth;      /* n_views out: DEPTH views; NaN for the others                                            */
+    int32_t  status;
+    int32_t  pad;
+} movba_view_result;    /* 88 bytes */
+
+/* Restated as written, item by item:
+ *   FRUSTUM  Pc = Rcw P + tcw; z = Pc_z < 0 rejects; u = fx x / z + cx, v = fy y / z + cy; u < minX || u > maxX rejects, then the
+ *            same for v; dist = |P - Ow|; dist < 0.8 min_distance || dist > 1.2 max_distance rejects; view_cos = PO.Pn / dist <
+ *            cos_limit rejects; level = ceil(log(max_distance / dist) / log_scale_factor) clamped to [0, n_levels - 1]; ur = u -
+ *            bf / z; track_depth = |Pc|.  The clamp is applied to the real number before it becomes an integer: NaN gives 0 and
+ *            +inf gives n_levels - 1, where the reference's conversion is undefined.
+ *   FUSE     the same up to the projection; then IsInImage, half-open: u >= minX && u < maxX && v >= minY && v < maxY; the same
+ *            distance gate; PO.Pn < 0.5 dist rejects, without the division; no level is predicted.
+ *   DEPTH    z = (row 2 of Rcw) . P + t_z only.  median_depth is element (n - 1) / q, integer division, of the ascending order of the
+ *            view's z (KeyFrame.cc:788-790): exactly, by a radix select over the total order of bit patterns that movba_init_map's
+ *            median uses (-0 below +0, a positive NaN above +inf).  An empty list gives -1.0, the reference's N == 0 return (:759);
+ *            the reference reads out of bounds when N > 0 but no slot holds a point, and that case is an empty list here too.
+ * Comparisons as written: a NaN in a point, a normal or a distance passes them as it does there (z = 0 passes the depth test and
+ * projects to an infinity or a NaN).  The reference computes in float; this call is fp64 from the boundary to the result (as the
+ * LBA), so its decisions can differ from the reference's only for items within float rounding of a gate.
+ * The result of an item depends on that item and its view alone, and the result of a view on its own list alone - not on the
+ * other views, their order, or how the lists are split over calls - and two calls give the same bits: n_accepted is an integer
+ * count, the median is selected, not averaged, and there are no floating-point atomics.
+ * Returns MOVBA_ERR_ARG for a NULL handle, descriptor or result; a negative count; n_views > MOVBA_MAX_VIEW_BATCH; n_items above
+ * 2^28; view_ptr not ascending or not starting at 0; a point index out of range; an unknown mode; a NULL array that the counts or
+ * the modes make necessary (see the fields); fx or fy not positive and finite; any other per-view number that is given and not
+ * finite; n_levels < 1; q < 1 on a DEPTH view; log_scale_factor not positive on a FRUSTUM view; a zero quaternion.  MOVBA_ERR_HIP
+ * as elsewhere.  Every argument is checked before anything is queued, and on a non-zero status nothing is written except
+ * `status`.  No views: MOVBA_OK and nothing else written.  The contents of points, normals and distances may be anything.
+ * One packed copy to the device, two launches - k_vp_items, one thread per item over all items of the call, and k_vp_views, one
+ * workgroup per view: the count, and for DEPTH views the select, linear in the list: there is no limit like
+ * MOVBA_MAX_TWO_VIEW_MATCHES here - and one synchronisation; result arrays that lie in movba_host_alloc memory are written by the
+ * kernels themselves.  May share a handle with an uploaded or solved window, waiting for the window's arrays before it reuses
+ * the staging buffer: the window, its results and later runs stay as they were. */
+int  movba_view_points(movba_handle *h, const movba_view_desc *desc, movba_view_result *res);
+
 #ifdef __cplusplus
 }
 #endif

@@ -137,6 +137,17 @@ class InitMapTrace(C.Structure):
                 ("tr_rho", C.c_double * MAX_TRACE), ("tr_accept", C.c_int32 * MAX_TRACE)]
 
 
+class ViewDesc(C.Structure):
+    _fields_ = [("n_points", C.c_int32), ("n_views", C.c_int32), ("points", _d), ("normals", _d), ("max_distance", _d),
+                ("min_distance", _d), ("mode", _i), ("poses", _d), ("cam", _d), ("bf", _d), ("bounds", _d),
+                ("log_scale_factor", _d), ("n_levels", _i), ("cos_limit", _d), ("q", _i), ("view_ptr", _i), ("item_point", _i)]
+
+
+class ViewResult(C.Structure):
+    _fields_ = [("code", _u), ("z", _d), ("uv", _d), ("dist", _d), ("view_cos", _d), ("level", _i), ("ur", _d),
+                ("track_depth", _d), ("n_accepted", _i), ("median_depth", _d), ("status", C.c_int32), ("pad", C.c_int32)]
+
+
 MAX_INIT_MAP_ITERS = 100
 # movba_init_map_result::outcome (MOVBA_IM_*)
 IM_OK, IM_NEG_DEPTH, IM_FEW_TRACKED = 0, 1, 2
@@ -157,12 +168,21 @@ TRI_DLT, TRI_STEREO1, TRI_STEREO2 = 1, 2, 3
  TRI_REJ_ZERO_DIST, TRI_REJ_FAR) = range(16, 25)
 TRI_ACCEPTED = (TRI_DLT, TRI_STEREO1, TRI_STEREO2)
 
+# movba_view_desc::mode (MOVBA_VIEW_*)
+VIEW_FRUSTUM, VIEW_FUSE, VIEW_DEPTH = 0, 1, 2
+MAX_VIEW_BATCH = 4096
+# movba_view_result::code (MOVBA_VP_*): accepted ...
+VP_VISIBLE, VP_FUSE_CANDIDATE, VP_DEPTH_ITEM = 1, 2, 3
+# ... and rejected, in the order the reference tests
+VP_REJ_BEHIND, VP_REJ_U, VP_REJ_V, VP_REJ_IMAGE, VP_REJ_DIST, VP_REJ_ANGLE = range(16, 22)
+VP_ACCEPTED = (VP_VISIBLE, VP_FUSE_CANDIDATE, VP_DEPTH_ITEM)
+
 EXPORTS = ["movba_version", "movba_status_string", "movba_create", "movba_destroy", "movba_lba_solve",
            "movba_lba_upload", "movba_lba_reset", "movba_lba_run", "movba_lba_download",
            "movba_lba_export_poses_device", "movba_lba_set_pose_export", "movba_get_profile", "movba_reset_profile",
            "movba_structure_probe", "movba_pose_opt", "movba_set_profile_mask", "movba_lba_run_batch", "movba_pose_ransac_samples",
            "movba_host_alloc", "movba_host_free", "movba_dense_plan_probe", "movba_pose_opt_batch", "movba_lba_marginals", "movba_triangulate",
-           "movba_two_view", "movba_two_view_samples", "movba_two_view_lo", "movba_init_map"]
+           "movba_two_view", "movba_two_view_samples", "movba_two_view_lo", "movba_init_map", "movba_view_points"]
 
 _libs = {False: None, True: None}
 
@@ -223,6 +243,7 @@ def lib(hooks: bool = False):
         L.movba_two_view_lo.argtypes = [C.c_void_p, C.POINTER(TwoViewDesc), C.POINTER(TwoViewResult), C.c_int32, C.c_int32,
                                         C.POINTER(TwoViewLoInfo)]
         L.movba_init_map.argtypes = [C.c_void_p, C.POINTER(InitMapDesc), C.POINTER(InitMapResult), C.c_int32, C.POINTER(InitMapTrace)]
+        L.movba_view_points.argtypes = [C.c_void_p, C.POINTER(ViewDesc), C.POINTER(ViewResult)]
         L.movba_host_alloc.argtypes = [C.c_size_t]
         L.movba_host_alloc.restype = C.c_void_p
         L.movba_dense_plan_probe.argtypes = [C.c_int32, C.c_int32, C.c_int32, _i, _i, C.c_int32, _i, C.c_int32]
@@ -425,6 +446,59 @@ def init_map_desc(pair, alloc=np.zeros, chi2=True):
         keep["chi2"] = alloc((m, 2), np.float64)
         r.chi2 = _p(keep["chi2"], _d)
     return d, r, keep
+
+
+VIEW_DEFAULTS = dict(bf=0.0, bounds=(0.0, 0.0, 0.0, 0.0), log_scale_factor=float(np.log(1.2)), n_levels=8, cos_limit=0.5, q=2)
+# the optional per-item arrays of movba_view_result: name -> (entries per item, dtype)
+VIEW_ITEM_ARRAYS = dict(z=(1, np.float64), uv=(2, np.float64), dist=(1, np.float64), view_cos=(1, np.float64), level=(1, np.int32),
+                        ur=(1, np.float64), track_depth=(1, np.float64))
+
+
+def view_desc(points, views):
+    """points dict(points (N, 3), optional normals (N, 3), max_distance, min_distance (N,)), views: list of dicts with mode
+    (VIEW_*), pose (7,), cam (4,), items (indices into the point table) and optionally the keys of VIEW_DEFAULTS ->
+    (movba_view_desc, the arrays it points into).  The per-view arrays a mode does not read are still passed, with the
+    defaults."""
+    keep = dict(points=np.ascontiguousarray(points["points"], np.float64).reshape(-1, 3))
+    d = ViewDesc()
+    d.n_points = len(keep["points"]); d.points = _p(keep["points"], _d)
+    for key in ("normals", "max_distance", "min_distance"):
+        if points.get(key) is not None:
+            keep[key] = np.ascontiguousarray(points[key], np.float64)
+            setattr(d, key, _p(keep[key], _d))
+    nv = len(views)
+    d.n_views = nv
+    get = lambda v, key: v.get(key, VIEW_DEFAULTS[key])
+    keep["mode"] = np.array([v["mode"] for v in views], np.int32).reshape(nv)
+    keep["poses"] = np.array([v["pose"] for v in views], np.float64).reshape(nv, 7)
+    keep["cam"] = np.array([v["cam"] for v in views], np.float64).reshape(nv, 4)
+    keep["bf"] = np.array([get(v, "bf") for v in views], np.float64).reshape(nv)
+    keep["bounds"] = np.array([get(v, "bounds") for v in views], np.float64).reshape(nv, 4)
+    keep["log_scale_factor"] = np.array([get(v, "log_scale_factor") for v in views], np.float64).reshape(nv)
+    keep["n_levels"] = np.array([get(v, "n_levels") for v in views], np.int32).reshape(nv)
+    keep["cos_limit"] = np.array([get(v, "cos_limit") for v in views], np.float64).reshape(nv)
+    keep["q"] = np.array([get(v, "q") for v in views], np.int32).reshape(nv)
+    items = [np.asarray(v["items"], np.int32).reshape(-1) for v in views]
+    keep["view_ptr"] = np.concatenate([[0], np.cumsum([len(i) for i in items])]).astype(np.int32)
+    keep["item_point"] = np.ascontiguousarray(np.concatenate(items) if items else np.zeros(0), np.int32)
+    for key in ("poses", "cam", "bf", "bounds", "log_scale_factor", "cos_limit"):
+        setattr(d, key, _p(keep[key], _d))
+    for key in ("mode", "n_levels", "q", "view_ptr", "item_point"):
+        setattr(d, key, _p(keep[key], _i))
+    return d, keep
+
+
+def view_result(n_items, n_views, alloc=np.zeros, arrays=tuple(VIEW_ITEM_ARRAYS)):
+    """-> (movba_view_result with its output arrays, the arrays it points into); arrays: the optional per-item arrays asked
+    for (the others stay NULL)."""
+    keep = dict(code=alloc((n_items,), np.uint8), n_accepted=alloc((n_views,), np.int32), median_depth=alloc((n_views,), np.float64))
+    r = ViewResult()
+    r.code = _p(keep["code"], _u); r.n_accepted = _p(keep["n_accepted"], _i); r.median_depth = _p(keep["median_depth"], _d)
+    for key in arrays:
+        width, dtype = VIEW_ITEM_ARRAYS[key]
+        keep[key] = alloc((n_items, width) if width > 1 else (n_items,), dtype)
+        setattr(r, key, _p(keep[key], _i if dtype == np.int32 else _d))
+    return r, keep
 
 
 def run_batch(solvers) -> int:
@@ -752,4 +826,20 @@ class Solver:
                 o["trace"] = dict(lam=np.array(t.tr_lambda[:nt]), f0=np.array(t.tr_f0[:nt]), f1=np.array(t.tr_f1[:nt]),
                                   rho=np.array(t.tr_rho[:nt]), accept=np.array(t.tr_accept[:nt]))
             out.append(o)
+        return out
+
+    def view_points(self, points, views, pinned=False, arrays=tuple(VIEW_ITEM_ARRAYS)) -> dict:
+        """movba_view_points (Frame::isInFrustum, the gates at the head of MOVMatcher::Fuse, KeyFrame::ComputeSceneMedianDepth):
+        points dict(points (N, 3), normals (N, 3), max_distance, min_distance (N,) - the last three only when a view is not a
+        DEPTH view), views a list of dicts with mode (VIEW_*), pose (7,), cam (fx, fy, cx, cy), items (indices into the point
+        table) and optionally bf, bounds (minX, maxX, minY, maxY), log_scale_factor, n_levels, cos_limit, q ->
+        dict(status, view_ptr, code (uint8 VP_*) and the per-item arrays named in `arrays` (z, uv, dist, view_cos, level, ur,
+        track_depth) over all views' items in view order, n_accepted and median_depth per view).  pinned: result arrays in
+        movba_host_alloc memory (written by the kernels themselves; they live until close())."""
+        d, keep = view_desc(points, views)
+        r, out = view_result(len(keep["item_point"]), len(views), self._pinned if pinned else np.zeros, arrays)
+        rc = self._L.movba_view_points(self._h, C.byref(d), C.byref(r))
+        if rc < 0:
+            raise MovbaError(f"movba_view_points: {status_string(rc)}")
+        out.update(status=rc, view_ptr=keep["view_ptr"])
         return out
