@@ -742,6 +742,95 @@ typedef struct {
  * the staging buffer: the window, its results and later runs stay as they were. */
 int  movba_view_points(movba_handle *h, const movba_view_desc *desc, movba_view_result *res);
 
+/* The numeric body of MapPoint::UpdateNormalAndDepth (MapPoint.cc:362-435) for many map points per call: the mean viewing
+ * direction and the scale-invariance distances that movba_view_points takes as `normals`, `max_distance` and `min_distance`.
+ * The reference calls it after every step this library accelerates - LocalMapping::CreateNewMapPoints (LocalMapping.cc:488),
+ * SearchInNeighbors (:597), ProcessNewKeyFrame (:192), both bundle adjustments (Optimizer.cc:387, :837), both initialisations
+ * (Tracking.cc:542, :668, :715), Tracking::CreateNewKeyFrame (Tracking.cc:1082) and Map.cc:277.  The isBad test, the copy of the
+ * observations under the feature mutex (:367-375), the choice of mpRefKF and the lookup of the keypoint's octave (:409-423)
+ * stay with the caller: it passes the observers as index lists and the octave as a number. */
+typedef struct {
+    int32_t n_views;
+    int32_t n_points;
+    int32_t n_levels;               /* mnScaleLevels (:427), >= 1                                                          */
+    int32_t pad;
+    const double  *poses;           /* n_views x 7: qx qy qz qw tx ty tz = Tcw, as movba_view_desc::poses; the quaternion is
+                                       normalised before use; Ow = -Rcw^T tcw (KeyFrame::GetCameraCenter, :392, :406)       */
+    const double  *points;          /* n_points x 3, world: mWorldPos (:374)                                               */
+    const int32_t *obs_ptr;         /* n_points + 1: ascending prefix, obs_ptr[0] = 0; n_obs = obs_ptr[n_points]            */
+    const int32_t *obs_view;        /* n_obs: the observers of point p are [obs_ptr[p], obs_ptr[p + 1]), summed in this order
+                                       (mObservations, :372, :383-396)                                                     */
+    const int32_t *ref_view;        /* n_points: mpRefKF (:373) as a view index; it need not be in the point's list
+                                       (observations[pRefKF] at :409 does not require it either); the entry of a point with
+                                       an empty list is not read                                                           */
+    const int32_t *ref_level;       /* n_points: octave of the point's keypoint in the reference keyframe (:414),    
+                                       0 .. n_levels - 1                                                                   */
+    const double  *scale_factors;   /* n_levels: mvScaleFactors (:426, :432); one table per call - every frame of this fork has
+                                       the same 8 levels x 1.2 (Frame.cc:103-111)                                          */
+} movba_normals_desc;   /* 72 bytes */
+
+typedef struct {
+    double  *normals;               /* n_points x 3 out: mNormalVector (:433)                                              */
+    double  *max_distance;          /* n_points out: the raw mfMaxDistance (:431), what movba_view_desc::max_distance takes */
+    double  *min_distance;          /* n_points out: the raw mfMinDistance (:432)                                          */
+    int32_t  status;
+    int32_t  pad;
+} movba_normals_result; /* 32 bytes; each array is required when n_points > 0 */
+
+/* Restated as written, point by point, fp64 from the boundary to the result (the reference computes in float):
+ *   Ow_v   = -Rcw^T tcw of view v, from the pose, by the function movba_view_points derives it with: both calls agree on a
+ *            keyframe's centre to the bit.  Computed once per view.
+ *   acc = 0, n = 0; for each observer v of the point, strictly in list order (:383-396):
+ *            d = P - Ow_v; acc += d / sqrt(dx dx + dy dy + dz dz), a component-wise IEEE division, not a multiplication by a
+ *            reciprocal (:393-394); n++
+ *   normal = acc / (double)n (:433)
+ *   dist   = |P - Ow_ref|, ref = ref_view[p] (:406-407)
+ *   max_distance = dist * scale_factors[ref_level[p]] (:431)
+ *   min_distance = max_distance / scale_factors[n_levels - 1] (:432)
+ * A point with an empty list gets NaN in all five numbers: the reference returns at :377 and leaves the fields as they were.  A
+ * point lying in an observer's centre gives whatever the division gives (0 / 0), as it does there.  The reference sums in the
+ * iteration order of std::map<KeyFrame*, ...>, which is pointer order; here it is the caller's list order, and that is the only
+ * freedom: another order changes a normal by rounding only.  This fork's keyframes have NLeft == -1 and no right-camera
+ * observations, so the branches at :397-403 and :416-423 that read them are not restated.
+ * A point's result depends only on its own list in its order, the views it names, its ref_view and ref_level entries and the
+ * table - not on the other points, their order, or how the points are split over calls - and two calls give the same bits: the
+ * sum is sequential, there is no tree over a list and there are no floating-point atomics.
+ * Returns MOVBA_ERR_ARG for a NULL handle, descriptor or result; a negative count; n_obs above 2^28; a NULL array that the
+ * counts make necessary (obs_ptr, ref_level, scale_factors and the result arrays when n_points > 0; poses when n_views > 0;
+ * points, obs_view and ref_view when n_obs > 0); obs_ptr not ascending or not starting at 0; an observer index out of range; a
+ * ref_view that is read (a point with observers) out of range; a ref_level outside 0 .. n_levels - 1, or n_levels < 1; a scale
+ * factor that is not positive and finite; a pose entry that is not finite, or a zero quaternion.  MOVBA_ERR_HIP as elsewhere.
+ * Every argument is checked before anything is queued, and on a non-zero status nothing is written except `status`.  No points:
+ * MOVBA_OK and nothing else written.  The contents of `points` may be anything.
+ * One packed copy to the device, two launches - k_pn_centres, one thread per view, and k_pn_points, one thread per point walking
+ * its list: no limit on views or list length beyond the 2^28 observations, the centres live in device memory - and one
+ * synchronisation; result arrays that lie in movba_host_alloc memory are written by the kernels themselves.  May share a handle
+ * with an uploaded or solved window, waiting for the window's arrays before it reuses the staging buffer: the window, its
+ * results and later runs stay as they were. */
+int  movba_point_normals(movba_handle *h, const movba_normals_desc *desc, movba_normals_result *res);
+
+/* The same quantities for every map point of the handle's window after a run (Optimizer.cc:832-838), read out of the window
+ * where it lies on the device: the poses, the points and the observation lists do not cross the bus again.
+ *   the estimate   the one movba_lba_download returns
+ *   the observers  of point l: its uploaded edges in caller order (the upload's grouping by point is stable), as pose indices;
+ *                  edges whose outlier[e] is non-zero are skipped - the reference erases those observations at :809-818,
+ *                  before :837.  Re-choosing mpRefKF after an erasure (MapPoint::EraseObservation) stays with the caller.
+ *   ref_pose       n_points: mpRefKF as an index into the window's poses.  Every entry must be one, also that of a point whose
+ *                  edges are all skipped (the lists are on the device: the call cannot tell before it queues which are read)
+ *   ref_level      n_points, scale_factors n_levels: as movba_normals_desc
+ *   outlier        n_edges in caller edge order - what movba_lba_download returned - or NULL: no edge is skipped.  Copied by
+ *                  this call; never read through a pointer the window kept
+ *   normals, max_distance, min_distance   out, all required: as movba_normals_result; NaN for a point whose edges are all
+ *                  skipped
+ * Gives the bits of movba_point_normals fed the downloaded poses and points and the same lists (one kernel and one per-point
+ * function serve both).  Returns MOVBA_ERR_ARG (a NULL handle or array other than outlier, n_levels < 1, a ref_pose or ref_level
+ * out of range, a scale factor that is not positive and finite), MOVBA_ERR_STATE exactly where movba_lba_marginals gives it (no
+ * upload, no run since the upload / reset, or a run whose status was not MOVBA_OK) and MOVBA_ERR_HIP; on a non-zero status
+ * nothing is written.  Works after movba_lba_run_batch as well.  The window, its results, its marginals and later runs are left
+ * exactly as they were. */
+int  movba_lba_point_normals(movba_handle *h, const int32_t *ref_pose, const int32_t *ref_level, const double *scale_factors,
+                             int32_t n_levels, const uint8_t *outlier, double *normals, double *max_distance, double *min_distance);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,6 +11,7 @@
 #include <chrono>
 #include <condition_variable>
 #include <cstdio>
+#include <cstring>
 #include <functional>
 #include <mutex>
 #include <thread>
@@ -138,6 +139,24 @@ MOVBA_INTERNAL int ensure_stage(movba_handle *h, size_t bytes);
 MOVBA_INTERNAL int begin_side_call(movba_handle *h, size_t dev_bytes, size_t stage_bytes);
 // device view of [p, p + bytes) if it lies inside a movba_host_alloc block, else nullptr
 MOVBA_INTERNAL unsigned long long *host_block_view(const void *p, size_t bytes);
+
+// One result array of the caller: written by the kernels where it lies (movba_host_alloc memory), or into the staging buffer
+// and copied out behind the synchronisation; `dev` stays nullptr for an array the caller left out.
+template <typename T> struct Out {
+    T *user = nullptr, *dev = nullptr;
+    size_t off = 0, count = 0;
+    bool staged = false;
+    void plan(T *p, size_t n, Carver &c)
+    {
+        user = p; count = n;
+        if (!p || !n) return;
+        dev = reinterpret_cast<T *>(host_block_view(p, sizeof(T) * n));
+        staged = !dev;
+        if (staged) off = c.take<T>(n);
+    }
+    void bind(char *stage_dev) { if (staged) dev = reinterpret_cast<T *>(stage_dev + off); }
+    void fetch(const char *stage) const { if (staged) std::memcpy(user, stage + off, sizeof(T) * count); }
+};
 
 }  // namespace movba
 

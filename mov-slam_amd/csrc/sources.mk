@@ -1,9 +1,10 @@
 # The sources of libmovba, listed once.  Included by csrc/Makefile (the library and its test build; scripts/build_variant.sh
 # goes through it), by tests/hipstub/Makefile and tests/two_view_lo/Makefile (the host side alone, against the stand-in runtime and
 # the fake device) and by tests/init_map/Makefile (the same plus MOVBA_HOST_SRCS_OWN_FAKE and that directory's fake launch) and
-# by tests/view_points/Makefile (MOVBA_HOST_SRCS plus MOVBA_HOST_SRCS_VIEW and its own fake launch).
+# by tests/view_points/Makefile (MOVBA_HOST_SRCS plus MOVBA_HOST_SRCS_VIEW and its own fake launch) and by
+# tests/point_normals/Makefile (MOVBA_HOST_SRCS plus MOVBA_HOST_SRCS_NORMALS and its own fake launch).
 MOVBA_HIP_SRCS  := kernels.hip pcg_kernel.hip band_kernel.hip dense_solve.hip dense_persist.hip struct_kernels.hip struct_sort.hip \
-                   pose_kernels.hip marginals.hip triangulate.hip two_view.hip init_map.hip view_points.hip
+                   pose_kernels.hip marginals.hip triangulate.hip two_view.hip init_map.hip view_points.hip point_normals.hip
 MOVBA_HOST_SRCS := api.cpp upload.cpp structure.cpp dense_plan.cpp pcg_plan.cpp pose_opt.cpp marginals.cpp triangulate.cpp two_view.cpp
 # host sources whose launch the shared fake device does not stand in for: part of both libraries (csrc/Makefile), not of the
 # host-side builds that link MOVBA_HOST_SRCS against tests/hipstub's fixed set of fake launches (tests/init_map has its own)
@@ -11,5 +12,7 @@ MOVBA_HOST_SRCS_OWN_FAKE := init_map.cpp
 # the same for movba_view_points: a list of its own, because tests/init_map links MOVBA_HOST_SRCS_OWN_FAKE against that directory's
 # one fake launch (tests/view_points has the fake launch of this one)
 MOVBA_HOST_SRCS_VIEW := view_points.cpp
+# and for movba_point_normals / movba_lba_point_normals (tests/point_normals has their fake launch)
+MOVBA_HOST_SRCS_NORMALS := point_normals.cpp
 # host sources with a kernel file of the same stem: the kernels' object is <stem>_kernels.o
-MOVBA_SAME_STEM := marginals triangulate two_view init_map view_points
+MOVBA_SAME_STEM := marginals triangulate two_view init_map view_points point_normals

@@ -70,24 +70,6 @@ template <typename T> void put(char *stage, size_t off, const T *src, size_t cou
     std::memcpy(stage + off, src, sizeof(T) * count);
 }
 
-// One result array of the caller: written by the kernels where it lies (movba_host_alloc memory), or into the staging buffer
-// and copied out behind the synchronisation; `dev` stays nullptr for an array the caller left out.
-template <typename T> struct Out {
-    T *user = nullptr, *dev = nullptr;
-    size_t off = 0, count = 0;
-    bool staged = false;
-    void plan(T *p, size_t n, Carver &c)
-    {
-        user = p; count = n;
-        if (!p || !n) return;
-        dev = reinterpret_cast<T *>(host_block_view(p, sizeof(T) * n));
-        staged = !dev;
-        if (staged) off = c.take<T>(n);
-    }
-    void bind(char *stage_dev) { if (staged) dev = reinterpret_cast<T *>(stage_dev + off); }
-    void fetch(const char *stage) const { if (staged) std::memcpy(user, stage + off, sizeof(T) * count); }
-};
-
 }  // namespace
 
 extern "C" int movba_view_points(movba_handle *h, const movba_view_desc *desc, movba_view_result *res)

@@ -148,6 +148,15 @@ class ViewResult(C.Structure):
                 ("track_depth", _d), ("n_accepted", _i), ("median_depth", _d), ("status", C.c_int32), ("pad", C.c_int32)]
 
 
+class NormalsDesc(C.Structure):
+    _fields_ = [("n_views", C.c_int32), ("n_points", C.c_int32), ("n_levels", C.c_int32), ("pad", C.c_int32), ("poses", _d),
+                ("points", _d), ("obs_ptr", _i), ("obs_view", _i), ("ref_view", _i), ("ref_level", _i), ("scale_factors", _d)]
+
+
+class NormalsResult(C.Structure):
+    _fields_ = [("normals", _d), ("max_distance", _d), ("min_distance", _d), ("status", C.c_int32), ("pad", C.c_int32)]
+
+
 MAX_INIT_MAP_ITERS = 100
 # movba_init_map_result::outcome (MOVBA_IM_*)
 IM_OK, IM_NEG_DEPTH, IM_FEW_TRACKED = 0, 1, 2
@@ -182,7 +191,8 @@ EXPORTS = ["movba_version", "movba_status_string", "movba_create", "movba_destro
            "movba_lba_export_poses_device", "movba_lba_set_pose_export", "movba_get_profile", "movba_reset_profile",
            "movba_structure_probe", "movba_pose_opt", "movba_set_profile_mask", "movba_lba_run_batch", "movba_pose_ransac_samples",
            "movba_host_alloc", "movba_host_free", "movba_dense_plan_probe", "movba_pose_opt_batch", "movba_lba_marginals", "movba_triangulate",
-           "movba_two_view", "movba_two_view_samples", "movba_two_view_lo", "movba_init_map", "movba_view_points"]
+           "movba_two_view", "movba_two_view_samples", "movba_two_view_lo", "movba_init_map", "movba_view_points",
+           "movba_point_normals", "movba_lba_point_normals"]
 
 _libs = {False: None, True: None}
 
@@ -244,6 +254,8 @@ def lib(hooks: bool = False):
                                         C.POINTER(TwoViewLoInfo)]
         L.movba_init_map.argtypes = [C.c_void_p, C.POINTER(InitMapDesc), C.POINTER(InitMapResult), C.c_int32, C.POINTER(InitMapTrace)]
         L.movba_view_points.argtypes = [C.c_void_p, C.POINTER(ViewDesc), C.POINTER(ViewResult)]
+        L.movba_point_normals.argtypes = [C.c_void_p, C.POINTER(NormalsDesc), C.POINTER(NormalsResult)]
+        L.movba_lba_point_normals.argtypes = [C.c_void_p, _i, _i, _d, C.c_int32, _u, _d, _d, _d]
         L.movba_host_alloc.argtypes = [C.c_size_t]
         L.movba_host_alloc.restype = C.c_void_p
         L.movba_dense_plan_probe.argtypes = [C.c_int32, C.c_int32, C.c_int32, _i, _i, C.c_int32, _i, C.c_int32]
@@ -498,6 +510,32 @@ def view_result(n_items, n_views, alloc=np.zeros, arrays=tuple(VIEW_ITEM_ARRAYS)
         width, dtype = VIEW_ITEM_ARRAYS[key]
         keep[key] = alloc((n_items, width) if width > 1 else (n_items,), dtype)
         setattr(r, key, _p(keep[key], _i if dtype == np.int32 else _d))
+    return r, keep
+
+
+def normals_desc(points, views, lists, ref_view, ref_level, scale_factors):
+    """points (N, 3), views (V, 7) poses Tcw, lists: one sequence of view indices per point (its observers, in the order they
+    are summed), ref_view, ref_level (N,), scale_factors (L,) -> (movba_normals_desc, the arrays it points into)."""
+    keep = dict(points=np.ascontiguousarray(points, np.float64).reshape(-1, 3), poses=np.ascontiguousarray(views, np.float64).reshape(-1, 7),
+                ref_view=np.ascontiguousarray(ref_view, np.int32).reshape(-1), ref_level=np.ascontiguousarray(ref_level, np.int32).reshape(-1),
+                scale_factors=np.ascontiguousarray(scale_factors, np.float64).reshape(-1))
+    lists = [np.asarray(l, np.int32).reshape(-1) for l in lists]
+    keep["obs_ptr"] = np.concatenate([[0], np.cumsum([len(l) for l in lists])]).astype(np.int32)
+    keep["obs_view"] = np.ascontiguousarray(np.concatenate(lists) if lists else np.zeros(0), np.int32)
+    d = NormalsDesc()
+    d.n_views, d.n_points, d.n_levels = len(keep["poses"]), len(keep["points"]), len(keep["scale_factors"])
+    for key in ("poses", "points", "scale_factors"):
+        setattr(d, key, _p(keep[key], _d))
+    for key in ("obs_ptr", "obs_view", "ref_view", "ref_level"):
+        setattr(d, key, _p(keep[key], _i))
+    return d, keep
+
+
+def normals_result(n_points, alloc=np.zeros):
+    """-> (movba_normals_result with its output arrays, the arrays it points into)"""
+    keep = dict(normals=alloc((n_points, 3), np.float64), max_distance=alloc((n_points,), np.float64), min_distance=alloc((n_points,), np.float64))
+    r = NormalsResult()
+    r.normals = _p(keep["normals"], _d); r.max_distance = _p(keep["max_distance"], _d); r.min_distance = _p(keep["min_distance"], _d)
     return r, keep
 
 
@@ -842,4 +880,42 @@ class Solver:
         if rc < 0:
             raise MovbaError(f"movba_view_points: {status_string(rc)}")
         out.update(status=rc, view_ptr=keep["view_ptr"])
+        return out
+
+    def point_normals(self, points, views, lists, ref_view, ref_level, scale_factors, pinned=False) -> dict:
+        """movba_point_normals (the numeric body of MapPoint::UpdateNormalAndDepth): points (N, 3), views (V, 7) poses Tcw,
+        lists: one sequence of view indices per point (its observers, in the order they are summed), ref_view (N,) the
+        reference keyframe as a view index, ref_level (N,) the keypoint's octave there, scale_factors (L,) ->
+        dict(status, normals (N, 3), max_distance, min_distance (N,)): what view_points takes under those names; NaN for a
+        point without observers.  pinned: result arrays in movba_host_alloc memory (written by the kernel itself; they live
+        until close())."""
+        d, keep = normals_desc(points, views, lists, ref_view, ref_level, scale_factors)
+        r, out = normals_result(d.n_points, self._pinned if pinned else np.zeros)
+        rc = self._L.movba_point_normals(self._h, C.byref(d), C.byref(r))
+        if rc < 0:
+            raise MovbaError(f"movba_point_normals: {status_string(rc)}")
+        out.update(status=rc)
+        return out
+
+    def lba_point_normals(self, ref_pose, ref_level, scale_factors, outlier=None, pinned=False) -> dict:
+        """movba_lba_point_normals: the same quantities for every map point of the window of the last run, read where it lies
+        on the device.  ref_pose (P,) indexes the window's poses, ref_level (P,), scale_factors (L,); outlier: (E,) flags in
+        caller edge order (what download returned) whose edges are skipped, or None -> dict(status, normals (P, 3),
+        max_distance, min_distance (P,)).  pinned: as point_normals."""
+        d, keep = self._keep
+        ref_pose = np.ascontiguousarray(ref_pose, np.int32).reshape(-1)
+        ref_level = np.ascontiguousarray(ref_level, np.int32).reshape(-1)
+        scale = np.ascontiguousarray(scale_factors, np.float64).reshape(-1)
+        if len(ref_pose) != d.n_points or len(ref_level) != d.n_points:
+            raise ValueError("lba_point_normals: ref_pose and ref_level have one entry per map point of the window")
+        if outlier is not None:
+            outlier = np.ascontiguousarray(outlier, np.uint8).reshape(-1)
+            if len(outlier) != d.n_edges:
+                raise ValueError("lba_point_normals: outlier has one entry per edge of the window")
+        r, out = normals_result(d.n_points, self._pinned if pinned else np.zeros)
+        rc = self._L.movba_lba_point_normals(self._h, _p(ref_pose, _i), _p(ref_level, _i), _p(scale, _d), len(scale),
+                                             _p(outlier, _u) if outlier is not None else None, r.normals, r.max_distance, r.min_distance)
+        if rc < 0:
+            raise MovbaError(f"movba_lba_point_normals: {status_string(rc)}")
+        out.update(status=rc)
         return out
