@@ -467,26 +467,11 @@ __device__ __forceinline__ void band_body(const DevWindow &w, int bw_arg)
     const DevState &S0 = w.st[cur];
     const DevState &S1 = w.st[cur ^ 1];
     for (int i = tid; i < w.NP; i += kBT) {
-        double Tq[7], Tn[7];
+        double Tq[7];
 #pragma unroll
         for (int k = 0; k < 7; ++k) Tq[k] = S0.pose[7 * i + k];
         const int h = w.hidx[i];
-        if (h >= 0 && !fail) {          // (a failed factorisation moves nothing: g2o returns from solve() before its update)
-            double u[6];
-#pragma unroll
-            for (int k = 0; k < 6; ++k) u[k] = aux[6 * h + k];
-            se3_oplus(u, Tq, Tn);
-        } else {
-#pragma unroll
-            for (int k = 0; k < 7; ++k) Tn[k] = Tq[k];
-        }
-        double R[9];
-        quat_to_R(Tn, R);
-#pragma unroll
-        for (int k = 0; k < 7; ++k) S1.pose[7 * i + k] = Tn[k];
-#pragma unroll
-        for (int k = 0; k < 9; ++k) S1.Rt[12 * i + k] = R[k];
-        S1.Rt[12 * i + 9] = Tn[4]; S1.Rt[12 * i + 10] = Tn[5]; S1.Rt[12 * i + 11] = Tn[6];
+        store_trial_pose(S1.pose, S1.Rt, i, Tq, h, !fail, aux);
     }
     BAND_STAMP(5);
 #ifdef MOVBA_CLOCK_STAMP

@@ -31,6 +31,7 @@
 #include "dense_tile.h"
 #include "device_math.h"
 #include "device_types.h"
+#include "handoff.h"
 #include "kernels.h"
 
 namespace movba {
@@ -45,19 +46,7 @@ constexpr int kTaskCache = 128;                 // tasks of the workgroup's list
 __host__ __device__ constexpr int kTaskOff(int nslots) { return (2 + nslots) * kTileLds + 672; }       // (doubles) behind the carve
 __host__ __device__ constexpr int kBadOff(int nslots) { return (2 + nslots) * kTileLds + 660; }     // LDS word of sweep_inverse's bad-pivot flag (in the carve's spare doubles)
 
-// every word that travels between workgroups is a GLOBAL agent-scope access (global_load / global_store ... sc1, never flat_)
-typedef __attribute__((address_space(1))) long long g_i64;
-typedef __attribute__((address_space(1))) unsigned g_u32;
-__device__ __forceinline__ double ld_sc1(const double *p)
-{
-    return __longlong_as_double(__hip_atomic_load((const g_i64 *)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-}
-__device__ __forceinline__ void st_sc1(double *p, double v)
-{
-    __hip_atomic_store((g_i64 *)p, __double_as_longlong(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ unsigned ld_flag(const unsigned *p) { return __hip_atomic_load((const g_u32 *)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void st_flag(unsigned *p, unsigned v) { __hip_atomic_store((g_u32 *)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+// (every word that travels between workgroups is a GLOBAL agent-scope access: the hx_ primitives of handoff.h)
 
 struct Lds {
     double *A, *B;          // two scratch tiles (MFMA operands; the sweeps' column table spans both)
@@ -82,7 +71,6 @@ __device__ __forceinline__ Lds carve(double *sm, int nslots, unsigned long long 
 
 // global tile (row-major NB x NB) <-> LDS image (row stride LD): 16-byte sc1 (write-through / L1-bypassing) accesses through a
 // buffer descriptor of the tile, all of a thread's accesses in flight (a tile is 1 152 x 16 bytes: 4.5 per thread)
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 constexpr int kTileBytes = NB * NB * 8, kTileVec = kTileBytes / 16;
 // TRI = 2: an upper triangular tile (the inverse factor W_K) travels without its three 16 x 16 blocks below the diagonal
 // (TRI = 1: without those above)
@@ -91,8 +79,8 @@ __device__ __forceinline__ bool tri_skip(int row, int c) { return TRI == 1 ? (c 
 template <int TRI = 0>
 __device__ __forceinline__ void fetch_tile(const double *g, double *lds, int tid)
 {
-    const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(const_cast<double *>(g), 0, kTileBytes, 0x00020000);
-    u32x4 v[5];
+    const __amdgpu_buffer_rsrc_t r = hx_rsrc(g, kTileBytes);
+    hx_u32x4 v[5];
 #pragma unroll
     for (int q = 0; q < 5; ++q) {
         const int e = tid + kPT * q, row = (2 * e) / NB, c = 2 * e - row * NB;
@@ -113,7 +101,7 @@ __device__ __forceinline__ void fetch_tile(const double *g, double *lds, int tid
 template <int TRI = 0>
 __device__ __forceinline__ void publish_tile(double *g, const double *lds, int tid)
 {
-    const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(g, 0, kTileBytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t r = hx_rsrc(g, kTileBytes);
 #pragma unroll
     for (int q = 0; q < 5; ++q) {
         const int e = tid + kPT * q;
@@ -121,8 +109,7 @@ __device__ __forceinline__ void publish_tile(double *g, const double *lds, int t
             const int row = (2 * e) / NB, c = 2 * e - row * NB;
             if (tri_skip<TRI>(row, c)) continue;
             const double a = lds[row * LD + c], b = lds[row * LD + c + 1];
-            const u32x4 v = { (unsigned)__double2loint(a), (unsigned)__double2hiint(a), (unsigned)__double2loint(b), (unsigned)__double2hiint(b) };
-            __builtin_amdgcn_raw_buffer_store_b128(v, r, e * 16, 0, 16);
+            hx_st_f64x2(r, e * 16, a, b);
         }
     }
 }
@@ -130,26 +117,23 @@ __device__ __forceinline__ void publish_tile(double *g, const double *lds, int t
 // A 48-vector handed over as 48 self-announcing 16-byte records (value, the launch's epoch, a check word): one sc1 store per
 // lane, no drain, no flag; the consumer's lanes poll their own record until epoch and check word fit.  (A 16-byte store of one
 // lane is one request to one cache line; the check word is there so that a torn read could only ever cause another look.)
-constexpr unsigned kTagSalt = 0x9e3779b9u;
+// (the record: hx_st_tagged of handoff.h)
 __device__ __forceinline__ void st_tagged(unsigned *rec_base, int nrec_bytes, int t, double v, unsigned epoch)
 {
-    const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(rec_base, 0, nrec_bytes, 0x00020000);
-    const unsigned lo = (unsigned)__double2loint(v), hi = (unsigned)__double2hiint(v);
-    const u32x4 q = { lo, hi, epoch, epoch ^ lo ^ hi ^ kTagSalt };
-    __builtin_amdgcn_raw_buffer_store_b128(q, r, t * 16, 0, 16);
+    hx_st_tagged(hx_rsrc(rec_base, nrec_bytes), t, v, epoch);
 }
 // wave 0, lanes below 48: false (to the whole workgroup, through Lds::abort) when the records did not come within kWaitTicks
 __device__ __forceinline__ bool ld_tagged(const unsigned *rec_base, int nrec_bytes, int tid, unsigned epoch, double &v, const Lds &l)
 {
     if (tid < 64) {
-        const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned *>(rec_base), 0, nrec_bytes, 0x00020000);
+        const __amdgpu_buffer_rsrc_t r = hx_rsrc(rec_base, nrec_bytes);
         const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
         const bool mine = tid < NB;
         bool good = true;
-        u32x4 q;
+        hx_u32x4 q;
         for (;;) {
             q = __builtin_amdgcn_raw_buffer_load_b128(r, mine ? tid * 16 : 0, 0, 16);
-            const bool ok = q.z == epoch && q.w == (epoch ^ q.x ^ q.y ^ kTagSalt);
+            const bool ok = q.z == epoch && q.w == (epoch ^ q.x ^ q.y ^ kHxTagSalt);       // (hx_ld_tagged's test; the value is taken once, behind the loop)
             if (__all(ok || !mine)) break;
             if (__builtin_amdgcn_s_memrealtime() - t0 > l.wait_ticks) { good = false; break; }
             __builtin_amdgcn_s_sleep(1);
@@ -164,9 +148,9 @@ __device__ __forceinline__ bool ld_tagged(const unsigned *rec_base, int nrec_byt
 // every storing wave drains its stores, the workgroup meets, ONE lane stores the flag
 __device__ __forceinline__ void set_flag(unsigned *flags, int idx, unsigned epoch, int tid)
 {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    hx_drain();
     __syncthreads();
-    if (tid == 0) st_flag(flags + idx, epoch);
+    if (tid == 0) hx_st_u32(flags + idx, epoch);
 }
 
 // wave 0 polls n flags (lane i the i-th, 64 per pass) until all carry the epoch; the barrier behind releases the others.
@@ -182,7 +166,7 @@ __device__ __forceinline__ bool wg_wait(const unsigned *flags, unsigned epoch, i
             const unsigned *f = flags + idx(mine ? i : base);
             const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
             for (;;) {
-                const bool ok = ld_flag(f) == epoch;
+                const bool ok = hx_ld_u32(f) == epoch;
                 if (__all(ok || !mine)) break;
                 if (__builtin_amdgcn_s_memrealtime() - t0 > l.wait_ticks) { good = false; break; }
                 __builtin_amdgcn_s_sleep(2);
@@ -204,7 +188,7 @@ __device__ __forceinline__ int wg_wait2(const unsigned *flags, unsigned epoch, i
         unsigned long long m;
         bool good = true;
         for (;;) {
-            m = __ballot(ld_flag(f) == epoch);
+            m = __ballot(hx_ld_u32(f) == epoch);
             if (m & 1) break;
             if (__builtin_amdgcn_s_memrealtime() - t0 > l.wait_ticks) { good = false; break; }
             __builtin_amdgcn_s_sleep(2);
@@ -439,7 +423,7 @@ __device__ __attribute__((noinline)) void assemble_tile(AsmView av, int I, int K
             } else {
                 for (int itx = j0; itx < j1; ++itx) { bb += part[(size_t)itx * kPartStride + 63 + a]; cb += part[(size_t)itx * kPartStride + 36 + a]; }
             }
-            st_sc1(av.bp + gc, bb);
+            hx_st_f64(av.bp + gc, bb);
             v = bb - cb;
         }
         sm[rrow_off + tid] = v;
@@ -742,7 +726,7 @@ __global__ __launch_bounds__(kPT) void k_dense_persist(DevWindow w, unsigned epo
                 __syncthreads();
             }
             if (stamps && tid == 0) stamps[6 * (size_t)t + 2] = __builtin_amdgcn_s_memrealtime();
-            if (sweep_inverse(kTileLds, slot_off, kBadOff(nslots)) && tid == 0) st_flag(failw, epoch);
+            if (sweep_inverse(kTileLds, slot_off, kBadOff(nslots)) && tid == 0) hx_st_u32(failw, epoch);
             if (stamps && tid == 0) stamps[6 * (size_t)t + 3] = __builtin_amdgcn_s_memrealtime();
             publish_tile<2>(tiles + tile_off(K, K), slot, tid);
             set_flag(flags, dense_flag_PD(nt, K), epoch, tid);
@@ -765,7 +749,7 @@ __global__ __launch_bounds__(kPT) void k_dense_persist(DevWindow w, unsigned epo
             tile_update<true>(slot, sub, sub, wv, lane, l.B);           // D_K into scratch tile B (W_(K-1) is through)
             set_flag(flags, dense_flag_F(nt, K, K - 1), epoch, tid);
             if (stamps && tid == 0) stamps[6 * (size_t)t + 2] = __builtin_amdgcn_s_memrealtime();
-            if (sweep_inverse(kTileLds, slot_off, kBadOff(nslots)) && tid == 0) st_flag(failw, epoch);
+            if (sweep_inverse(kTileLds, slot_off, kBadOff(nslots)) && tid == 0) hx_st_u32(failw, epoch);
             if (stamps && tid == 0) stamps[6 * (size_t)t + 3] = __builtin_amdgcn_s_memrealtime();
 #ifdef MOVBA_SWEEP_PROFILE
             if (stamps && tid == 0 && K == 1) {
@@ -802,14 +786,14 @@ __global__ __launch_bounds__(kPT) void k_dense_persist(DevWindow w, unsigned epo
             if (K >= 1) {
                 if (!wg_wait(flags, epoch, 1, [&](int) { return dense_flag_F(nt, nt, K - 1); }, l, tid)) { aborted = true; break; }
                 if (stamps && tid == 0) stamps[6 * (size_t)t + 1] = __builtin_amdgcn_s_memrealtime();
-                if (tid < NB) l.xs[tid] = ld_sc1(tiles + tile_off(nt, K - 1) + tid);
+                if (tid < NB) l.xs[tid] = hx_ld_f64(tiles + tile_off(nt, K - 1) + tid);
                 __syncthreads();
                 rhs_minus_tile_times(sm + (2 + tk.pad[0]) * kTileLds, l, tid);       // L(K, K-1): the workgroup's own tile (pad[0] = its slot)
             }
             if (tid < NB) l.xs[tid] = l.rrow[tid];
             __syncthreads();
             const double yk = tile_matvec<true>(slot, l, tid);
-            if (tid < NB) { l.yv[tid] = yk; st_sc1(tiles + tile_off(nt, K) + tid, yk); }
+            if (tid < NB) { l.yv[tid] = yk; hx_st_f64(tiles + tile_off(nt, K) + tid, yk); }
             set_flag(flags, dense_flag_F(nt, nt, K), epoch, tid);
             break;
         }
@@ -818,7 +802,7 @@ __global__ __launch_bounds__(kPT) void k_dense_persist(DevWindow w, unsigned epo
             if (!wg_wait(flags, epoch, 1, [&](int) { return dense_flag_F(nt, nt, k); }, l, tid)) { aborted = true; break; }
             if (stamps && tid == 0) stamps[6 * (size_t)t + 1] = __builtin_amdgcn_s_memrealtime();
             fetch_tile(tiles + tile_off(K, k), l.A, tid);
-            if (tid < NB) l.xs[tid] = ld_sc1(tiles + tile_off(nt, k) + tid);
+            if (tid < NB) l.xs[tid] = hx_ld_f64(tiles + tile_off(nt, k) + tid);
             __syncthreads();
             rhs_minus_tile_times(l.A, l, tid);
             break;
@@ -835,7 +819,7 @@ __global__ __launch_bounds__(kPT) void k_dense_persist(DevWindow w, unsigned epo
                     for (int i0 = J + 2; i0 < nt; i0 += 8) {
                         double v[8];
 #pragma unroll
-                        for (int u = 0; u < 8; ++u) v[u] = i0 + u < nt ? ld_sc1(contrib + ((size_t)(i0 + u) * nt + J) * NB + tid) : 0.0;
+                        for (int u = 0; u < 8; ++u) v[u] = i0 + u < nt ? hx_ld_f64(contrib + ((size_t)(i0 + u) * nt + J) * NB + tid) : 0.0;
 #pragma unroll
                         for (int u = 0; u < 8; ++u) acc += v[u];
                     }
@@ -851,7 +835,7 @@ __global__ __launch_bounds__(kPT) void k_dense_persist(DevWindow w, unsigned epo
             __syncthreads();
             const double xj = tile_matvec<false>(slot, l, tid);       // x_J = W_J (y_J - sum c(I, J))
             __syncthreads();                                                   // (every thread is through with xs and ps)
-            if (tid < NB) { l.xv[tid] = xj; l.xs[tid] = xj; st_sc1(xsol + J * NB + tid, xj); }
+            if (tid < NB) { l.xv[tid] = xj; l.xs[tid] = xj; hx_st_f64(xsol + J * NB + tid, xj); }
             if (J >= 1) {
                 // c(J, J-1) = L(J, J-1)^T x_J straight away (the owner's own tile), handed to block row J - 1 as tagged records
                 __syncthreads();
@@ -869,7 +853,7 @@ __global__ __launch_bounds__(kPT) void k_dense_persist(DevWindow w, unsigned epo
                 flush();
                 if (!wg_wait(flags, epoch, 1, [&](int) { return dense_flag_FX(nt, I); }, l, tid)) { aborted = true; break; }
                 if (stamps && tid == 0) stamps[6 * (size_t)t + 1] = __builtin_amdgcn_s_memrealtime();
-                if (tid < NB) l.xs[tid] = ld_sc1(xsol + I * NB + tid);
+                if (tid < NB) l.xs[tid] = hx_ld_f64(xsol + I * NB + tid);
             } else if (tid < NB) l.xs[tid] = l.xv[tid];
             __syncthreads();
             const int g = tid / NB, cc = tid - g * NB;
@@ -881,9 +865,9 @@ __global__ __launch_bounds__(kPT) void k_dense_persist(DevWindow w, unsigned epo
             }
             __syncthreads();
             const double cv = tid < NB ? (((l.ps[tid] + l.ps[NB + tid]) + l.ps[2 * NB + tid]) + l.ps[3 * NB + tid]) + l.ps[4 * NB + tid] : 0.0;
-            if (tid < NB) st_sc1(contrib + ((size_t)I * nt + K) * NB + tid, cv);
+            if (tid < NB) hx_st_f64(contrib + ((size_t)I * nt + K) * NB + tid, cv);
             set_flag(flags, dense_flag_FC(nt, I, K), epoch, tid);
-            if (pending >= 0) { if (tid == 0) st_flag(flags + pending, epoch); pending = -1; }      // (x_I's stores were drained by the same wait)
+            if (pending >= 0) { if (tid == 0) hx_st_u32(flags + pending, epoch); pending = -1; }      // (x_I's stores were drained by the same wait)
             break;
         }
         case DT_EPI: {
@@ -898,19 +882,19 @@ __global__ __launch_bounds__(kPT) void k_dense_persist(DevWindow w, unsigned epo
     }
     flush();
     if (blockIdx.x != 0) {
-        if (aborted && tid == 0) st_flag(failw + 1, epoch);
+        if (aborted && tid == 0) hx_st_u32(failw + 1, epoch);
         return;
     }
 
     // ---- workgroup 0: increment, pose part of computeScale(), trial poses (VertexSE3Expmap::oplusImpl); releases a parked
     // solve (Ctrl::done 2 -> 0).  A solve that gave up on a wait is reported as a failed factorisation AND counted. ----
     __syncthreads();
-    const bool fail = aborted || ld_flag(failw) == epoch || ld_flag(failw + 1) == epoch;
+    const bool fail = aborted || hx_ld_u32(failw) == epoch || hx_ld_u32(failw + 1) == epoch;
     double *x = l.A;                                // n <= 2 tiles of scratch (dense_persist_supported)
     double sc = 0.0;
     for (int idx = tid; idx < n; idx += kPT) {
-        const double xv = fail ? 0.0 : ld_sc1(xsol + idx);
-        const double bpv = fail ? 0.0 : ld_sc1(w.bp + idx);
+        const double xv = fail ? 0.0 : hx_ld_f64(xsol + idx);
+        const double bpv = fail ? 0.0 : hx_ld_f64(w.bp + idx);
         w.xp[idx] = xv;
         sc += xv * (lambda * xv + bpv);
         x[idx] = xv;
@@ -920,26 +904,11 @@ __global__ __launch_bounds__(kPT) void k_dense_persist(DevWindow w, unsigned epo
     const DevState &S0 = w.st[cur];
     const DevState &S1 = w.st[cur ^ 1];
     for (int i = tid; i < w.NP; i += kPT) {
-        double T[7], Tn[7];
+        double T[7];
 #pragma unroll
         for (int q = 0; q < 7; ++q) T[q] = S0.pose[7 * i + q];
         const int h = w.hidx[i];
-        if (h >= 0 && !fail) {          // (a failed factorisation moves nothing: g2o returns from solve() before its update)
-            double u[6];
-#pragma unroll
-            for (int q = 0; q < 6; ++q) u[q] = x[6 * h + q];
-            se3_oplus(u, T, Tn);
-        } else {
-#pragma unroll
-            for (int q = 0; q < 7; ++q) Tn[q] = T[q];
-        }
-        double R[9];
-        quat_to_R(Tn, R);
-#pragma unroll
-        for (int q = 0; q < 7; ++q) S1.pose[7 * i + q] = Tn[q];
-#pragma unroll
-        for (int q = 0; q < 9; ++q) S1.Rt[12 * i + q] = R[q];
-        S1.Rt[12 * i + 9] = Tn[4]; S1.Rt[12 * i + 10] = Tn[5]; S1.Rt[12 * i + 11] = Tn[6];
+        store_trial_pose(S1.pose, S1.Rt, i, T, h, !fail, x);
     }
     if (tid == 0) {
         w.scale_part[w.n_pt_blocks] = scs;
@@ -947,7 +916,7 @@ __global__ __launch_bounds__(kPT) void k_dense_persist(DevWindow w, unsigned epo
         c->pcg_last_iters = -1;                     // trace marker: this trial was solved directly
         c->n_direct += 1;
         if (fail) c->n_chol_fail += 1;
-        if (aborted || ld_flag(failw + 1) == epoch) c->n_sync_timeouts += 1;
+        if (aborted || hx_ld_u32(failw + 1) == epoch) c->n_sync_timeouts += 1;
         if (c->done == 2) c->done = 0;              // the solve was parked for this: the kernels behind run again
     }
 }

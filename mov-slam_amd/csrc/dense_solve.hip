@@ -384,26 +384,11 @@ __global__ __launch_bounds__(kBackThreads) void k_dense_backsolve(DevWindow w)
     const DevState &S0 = w.st[cur];
     const DevState &S1 = w.st[cur ^ 1];
     for (int i = tid; i < w.NP; i += kBackThreads) {
-        double T[7], Tn[7];
+        double T[7];
 #pragma unroll
         for (int k = 0; k < 7; ++k) T[k] = S0.pose[7 * i + k];
         const int h = w.hidx[i];
-        if (h >= 0 && !fail) {          // (a failed factorisation moves nothing: g2o returns from solve() before its update)
-            double u[6];
-#pragma unroll
-            for (int k = 0; k < 6; ++k) u[k] = x[6 * h + k];
-            se3_oplus(u, T, Tn);
-        } else {
-#pragma unroll
-            for (int k = 0; k < 7; ++k) Tn[k] = T[k];
-        }
-        double R[9];
-        quat_to_R(Tn, R);
-#pragma unroll
-        for (int k = 0; k < 7; ++k) S1.pose[7 * i + k] = Tn[k];
-#pragma unroll
-        for (int k = 0; k < 9; ++k) S1.Rt[12 * i + k] = R[k];
-        S1.Rt[12 * i + 9] = Tn[4]; S1.Rt[12 * i + 10] = Tn[5]; S1.Rt[12 * i + 11] = Tn[6];
+        store_trial_pose(S1.pose, S1.Rt, i, T, h, !fail, x);
     }
     if (tid == 0) {
         w.scale_part[w.n_pt_blocks] = scs;

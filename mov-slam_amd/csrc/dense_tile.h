@@ -36,14 +36,15 @@ __device__ __forceinline__ void load_tile(const double *__restrict__ g, double *
 
 // One wave's share of  C -= A B^T  for 48 x 48 tiles: MFMA tile (mt, nt) of 16 x 16, k = 48 in 12 steps of 4.
 // Operand maps of v_mfma_f64_16x16x4_f64: A[i = lane & 15][k = lane >> 4], B[k = lane >> 4][j = lane & 15],
-// C/D: col = lane & 15, row = (lane >> 4) + 4 reg.  A is negated on the way in, so D = C - A B^T.
+// C/D: col = lane & 15, row = (lane >> 4) + 4 reg.  A is negated on the way in, so D = C - A B^T (NEG = false: D = C + A B^T).
+template <bool NEG = true>
 __device__ __forceinline__ dbl4 tile_mfma(const double *As, const double *Bs, int mt, int nt, int lane, dbl4 c)
 {
     const double *ap = As + (mt * 16 + (lane & 15)) * LD + (lane >> 4);
     const double *bp = Bs + (nt * 16 + (lane & 15)) * LD + (lane >> 4);
     double a[NB / 4], b[NB / 4];                    // (operands in registers first: 24 LDS reads in flight, then the chain)
 #pragma unroll
-    for (int q = 0; q < NB / 4; ++q) { a[q] = -ap[4 * q]; b[q] = bp[4 * q]; }
+    for (int q = 0; q < NB / 4; ++q) { a[q] = NEG ? -ap[4 * q] : ap[4 * q]; b[q] = bp[4 * q]; }
 #pragma unroll
     for (int q = 0; q < NB / 4; ++q) c = __builtin_amdgcn_mfma_f64_16x16x4f64(a[q], b[q], c, 0, 0, 0);
     return c;

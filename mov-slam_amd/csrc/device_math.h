@@ -1,6 +1,7 @@
 // Small fp64 device helpers shared by the HIP kernels: SE3Quat arithmetic as g2o defines it
 // (normalizeRotation, operator*, exp — SURVEY.md Appendix A.8), Eigen's quaternion <-> matrix
-// conversions, the cofactor 3x3 inverse, fixed-order wave / block reductions, and the dense 6 x 6 Cholesky solve of the
+// conversions, the pose step and pose store of the reduced solvers' epilogues, the cofactor 3x3 inverse, fixed-order wave /
+// block / workgroup reductions, the prefix search of the batched grids, and the dense 6 x 6 Cholesky solve of the
 // single-workgroup LM kernels (pose_kernels.hip, init_map.hip).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -44,6 +45,7 @@ __device__ __forceinline__ double fast_rcp_zero_safe(double p)
     return p == 0.0 ? r0 : r;
 }
 
+// (not merged with pose_kernels.hip's R2q and two_view_math.h's tv_R2q: rsqrt and products here, sqrt and a division there)
 __device__ __forceinline__ void R_to_quat(const double m[9], double q[4])
 {
     double t = m[0] + m[4] + m[8];
@@ -158,6 +160,35 @@ __device__ inline void se3_oplus(const double u[6], const double T[7], double ou
     out[4] = e[4] + rt[0]; out[5] = e[5] + rt[1]; out[6] = e[6] + rt[2];
 }
 
+// pose i of a state (7 doubles) and its Rt cache (12: the rotation matrix row-major, then the translation)
+__device__ __forceinline__ void store_pose_rt(double *pose, double *Rt, int i, const double T[7])
+{
+    double R[9];
+    quat_to_R(T, R);
+#pragma unroll
+    for (int k = 0; k < 7; ++k) pose[7 * i + k] = T[k];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) Rt[12 * i + k] = R[k];
+    Rt[12 * i + 9] = T[4]; Rt[12 * i + 10] = T[5]; Rt[12 * i + 11] = T[6];
+}
+
+// the trial pose of a reduced solve into the other state: T <- exp(x_h) * T for a free keyframe (h >= 0: its block of the
+// increment x, in LDS), T itself for a fixed one or when nothing moved
+__device__ __forceinline__ void store_trial_pose(double *pose, double *Rt, int i, const double T[7], int h, bool moved, const double *x)
+{
+    double Tn[7];
+    if (h >= 0 && moved) {              // (a failed factorisation moves nothing: g2o returns from solve() before its update)
+        double u[6];
+#pragma unroll
+        for (int k = 0; k < 6; ++k) u[k] = x[6 * h + k];
+        se3_oplus(u, T, Tn);
+    } else {
+#pragma unroll
+        for (int k = 0; k < 7; ++k) Tn[k] = T[k];
+    }
+    store_pose_rt(pose, Rt, i, Tn);
+}
+
 // inverse of the symmetric 3x3 (xx xy xz yy yz zz) by cofactors
 __device__ __forceinline__ void inv3sym(const double A[6], double B[6])
 {
@@ -227,8 +258,6 @@ __device__ __forceinline__ double group_sum_dpp(double v, int G)
 }
 
 // (DPP trees: a butterfly of 64-bit __shfl_xor costs two ds_bpermute through the LDS crossbar per step)
-__device__ __forceinline__ double wave_sum(double v) { return wave_sum_dpp(v); }
-
 __device__ __forceinline__ double wave_max(double v)
 {
     v = fmax(v, dpp_mov0<0xb1>(v));
@@ -246,7 +275,7 @@ __device__ __forceinline__ double wave_max(double v)
 template <int NWAVES, bool MAX>
 __device__ __forceinline__ double block_reduce(double v, double *red /* NWAVES doubles in LDS */)
 {
-    v = MAX ? wave_max(v) : wave_sum(v);
+    v = MAX ? wave_max(v) : wave_sum_dpp(v);
     const int wave = threadIdx.x >> 6;
     if ((threadIdx.x & 63) == 0) red[wave] = v;
     __syncthreads();
@@ -255,6 +284,86 @@ __device__ __forceinline__ double block_reduce(double v, double *red /* NWAVES d
     for (int k = 1; k < NWAVES; ++k) s = MAX ? fmax(s, red[k]) : s + red[k];
     __syncthreads();
     return s;
+}
+
+// Fixed-order reduction of NV per-lane values over the 64 lanes of a wave: two DPP steps sum each quad,
+// the 16 quad sums of every value go through a wave-private LDS strip ([NV][16] doubles) and lane k < NV
+// adds them up in order (returned in lane k; its eight 16-byte reads are all in flight before the first add).  ~2k cycles
+// for NV = 54, against ~30k for NV butterfly reductions built on ds_bpermute shuffles.
+template <int NV>
+__device__ __forceinline__ double wave_reduce(double (&v)[NV], double *strip, int lane)
+{
+#pragma unroll
+    for (int k = 0; k < NV; ++k) {
+        double t = v[k];
+        t += dpp_mov0<0xb1>(t);
+        t += dpp_mov0<0x4e>(t);
+        if ((lane & 3) == 0) strip[k * 16 + (lane >> 2)] = t;
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    double s = 0.0;
+    if (lane < NV) {
+        const double2 *src = reinterpret_cast<const double2 *>(strip + lane * 16);
+        double2 t[8];
+#pragma unroll
+        for (int q = 0; q < 8; ++q) t[q] = src[q];
+#pragma unroll
+        for (int q = 0; q < 8; ++q) { s += t[q].x; s += t[q].y; }
+    }
+    return s;                                   // lane k < NV holds the wave's sum of value k
+}
+
+// fixed-order reduction of NV values per thread over a workgroup of NW waves; result in every thread (wave-uniform: scalar
+// registers).  Inside a wave: wave_reduce (a butterfly of 64-bit shuffles per value costs ~500 cycles each: 28 of them were
+// three quarters of an LM iteration); one or two values take the whole-wave DPP tree instead.  Then ONE workgroup barrier: lane
+// k of EVERY wave adds the waves' sums of value k in wave order and the values go round by v_readlane - an earlier form had
+// every thread read all NW x NV sums back from LDS itself behind a second barrier (112 eight-byte loads of a lone wave per
+// SIMD: 1 400 of the reduction's 3 600 cycles).  The waves' sums alternate between two places (`flip`), so a wave that runs
+// ahead into the next reduction cannot overwrite what a slower one still reads: it stops at that reduction's barrier first.
+// `lds`: kRedLds<NW> doubles, 16-byte aligned: the waves' sums (two places), then a strip per wave.
+constexpr int kRedMax = 28;
+template <int NW> constexpr int kRedLds = 2 * NW * kRedMax + NW * kRedMax * 16;
+template <int NW, int NV>
+__device__ __forceinline__ void reduce_all(double (&v)[NV], double *lds, int &flip)
+{
+    static_assert(NV <= kRedMax, "reduce_all: LDS strips sized for 28 values");
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    double *cross = lds + flip * (NW * kRedMax);
+    flip ^= 1;
+    if (NV <= 2) {
+#pragma unroll
+        for (int k = 0; k < NV; ++k) {
+            const double t = wave_sum_dpp(v[k]);
+            if (lane == 0) cross[wave * NV + k] = t;
+        }
+    } else {
+        const double s = wave_reduce(v, lds + 2 * NW * kRedMax + wave * (NV * 16), lane);
+        if (lane < NV) cross[wave * NV + lane] = s;
+    }
+    __syncthreads();
+    const int kk = lane < NV ? lane : NV - 1;
+    double w[NW];
+#pragma unroll
+    for (int q = 0; q < NW; ++q) w[q] = cross[q * NV + kk];
+    double tot = w[0];
+#pragma unroll
+    for (int q = 1; q < NW; ++q) tot += w[q];
+#pragma unroll
+    for (int k = 0; k < NV; ++k) v[k] = readlane_f64(tot, k);
+}
+
+// the segment that holds b in a prefix of segment sizes (a grid over concatenated windows, pairs or frames): the largest p < n
+// with first[p] <= b (first[n] > b: empty segments are never found)
+__device__ __forceinline__ int prefix_find(const int32_t *__restrict__ first, int n, int b)
+{
+    int lo = 0, hi = n - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (first[mid] <= b) lo = mid; else hi = mid - 1;
+    }
+    return lo;
 }
 
 // upper-triangle index of a symmetric 6x6, a <= b

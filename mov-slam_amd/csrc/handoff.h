@@ -3,7 +3,7 @@
 // at once (`global_store ... sc1`), loads bypass the CU's L1 (`global_load ... sc1`), never flat_, never through the scalar
 // cache.  Producer: sc1 stores, `s_waitcnt vmcnt(0)` in every storing wave, then ONE lane signals (an sc1 flag store or an
 // agent-scope atomic add); consumer: learns it from an sc1 poll or from the value its own add returned, and reads the bytes
-// with sc1 loads only.  dense_persist.hip keeps its own copies of the 8-byte forms (same instructions).
+// with sc1 loads only.  One copy: k_dense_persist's tile and vector hand-offs (dense_persist.hip) are built on these too.
 #pragma once
 #include <hip/hip_runtime.h>
 

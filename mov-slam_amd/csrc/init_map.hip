@@ -22,55 +22,6 @@ namespace {
 constexpr int kT = kImThreads;
 constexpr int kW = kT / 64;
 
-// Fixed-order sum of NV values per thread over the workgroup, result in every thread (pose_kernels.hip's reduce_all is the
-// model).  Inside a wave two DPP steps sum each quad, the 16 quad sums of every value cross a wave-private LDS strip and lane k
-// adds those of value k up in order; one workgroup barrier; lane k of every wave adds the waves' sums of value k in wave order.
-// The waves' sums alternate between two places (`flip`): a wave that runs ahead into the next reduction stops at that
-// reduction's barrier before it could overwrite what a slower one still reads.
-constexpr int kRedMax = 28;
-constexpr int kRedLds = 2 * kW * kRedMax + kW * kRedMax * 16;
-template <int NV>
-__device__ __forceinline__ void im_reduce(double (&v)[NV], double *lds /* kRedLds */, int &flip)
-{
-    static_assert(NV <= kRedMax, "im_reduce: LDS strips sized for 28 values");
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    double *cross = lds + flip * (kW * kRedMax);
-    flip ^= 1;
-    if (NV <= 2) {
-#pragma unroll
-        for (int k = 0; k < NV; ++k) {
-            const double t = wave_sum_dpp(v[k]);
-            if (lane == 0) cross[wave * NV + k] = t;
-        }
-    } else {
-        double *strip = lds + 2 * kW * kRedMax + wave * (NV * 16);
-#pragma unroll
-        for (int k = 0; k < NV; ++k) {
-            double t = v[k];
-            t += dpp_mov0<0xb1>(t);
-            t += dpp_mov0<0x4e>(t);
-            if ((lane & 3) == 0) strip[k * 16 + (lane >> 2)] = t;
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        if (lane < NV) {
-            const double *src = strip + lane * 16;
-            double s = 0.0;
-#pragma unroll
-            for (int q = 0; q < 16; ++q) s += src[q];
-            cross[wave * NV + lane] = s;
-        }
-    }
-    __syncthreads();
-    const int kk = lane < NV ? lane : NV - 1;
-    double tot = cross[kk];
-#pragma unroll
-    for (int q = 1; q < kW; ++q) tot += cross[q * NV + kk];
-#pragma unroll
-    for (int k = 0; k < NV; ++k) v[k] = readlane_f64(tot, k);
-}
-
 __device__ __forceinline__ void load3(const double *a, size_t cap, int k, double v[3])
 {
     v[0] = a[k]; v[1] = a[cap + k]; v[2] = a[2 * cap + k];
@@ -84,7 +35,7 @@ __device__ __forceinline__ void store3(double *a, size_t cap, int k, const doubl
 
 __global__ __launch_bounds__(kImThreads) void k_init_map(ImDev d)
 {
-    __shared__ double red[kRedLds];
+    __shared__ __attribute__((aligned(16))) double red[kRedLds<kW>];      // reduce_all (device_math.h)
     __shared__ double s_med;
     __shared__ int s_cnt[kW];
     const ImPair p = d.pairs[blockIdx.x];
@@ -148,7 +99,7 @@ __global__ __launch_bounds__(kImThreads) void k_init_map(ImDev d)
             for (int e = 0; e < kImLin; ++e) lin[(size_t)e * cap + k] = l[e];
             md = fmax(fmax(fabs(l[0]), fabs(l[3])), fmax(fabs(l[5]), md));
         }
-        im_reduce(acc, red, flip);
+        reduce_all<kW>(acc, red, flip);
         double F0 = acc[27];
         if (it == 0) {
             // computeLambdaInit: 1e-5 max |H_jj| over the pose block and the point blocks
@@ -172,7 +123,7 @@ __global__ __launch_bounds__(kImThreads) void k_init_map(ImDev d)
                 for (int e = 0; e < kImLin; ++e) l[e] = lin[(size_t)e * cap + k];
                 im_schur(l, lambda, sc);
             }
-            im_reduce(sc, red, flip);
+            reduce_all<kW>(sc, red, flip);
             double Su[21], bS[6], xp[6];
 #pragma unroll
             for (int e = 0; e < 21; ++e) Su[e] = acc[e] - sc[e];
@@ -201,7 +152,7 @@ __global__ __launch_bounds__(kImThreads) void k_init_map(ImDev d)
                 }
                 fs[0] += im_cost(Rt, trial + 4, cam, huber, x, d.obs1 + 2 * m, d.obs2 + 2 * m, d.sig1[m], d.sig2[m], c2);
             }
-            im_reduce(fs, red, flip);
+            reduce_all<kW>(fs, red, flip);
             double F1 = fs[0], scale = 0.0;
             if (ok2) {
 #pragma unroll
@@ -264,7 +215,7 @@ __global__ __launch_bounds__(kImThreads) void k_init_map(ImDev d)
         if (p.chi2) { p.chi2[2 * (size_t)i] = c2[0]; p.chi2[2 * (size_t)i + 1] = c2[1]; }
         z[k] = x[2];
     }
-    im_reduce(fc, red, flip);                               // (its barrier also publishes z to the workgroup)
+    reduce_all<kW>(fc, red, flip);                               // (its barrier also publishes z to the workgroup)
     const double cost = fc[0];
     if (p.max_iters == 0) cost0 = cost;
 

@@ -61,13 +61,7 @@ __device__ __forceinline__ void init_pose_body(const DevWindow &w, int bid, int 
 #pragma unroll
     for (int k = 0; k < 7; ++k) q[k] = w.pose0[7 * i + k];
     quat_normalize_exact(q);
-    double R[9];
-    quat_to_R(q, R);
-#pragma unroll
-    for (int k = 0; k < 7; ++k) w.st[0].pose[7 * i + k] = q[k];
-#pragma unroll
-    for (int k = 0; k < 9; ++k) w.st[0].Rt[12 * i + k] = R[k];
-    w.st[0].Rt[12 * i + 9] = q[4]; w.st[0].Rt[12 * i + 10] = q[5]; w.st[0].Rt[12 * i + 11] = q[6];
+    store_pose_rt(w.st[0].pose, w.st[0].Rt, i, q);
 }
 
 // The camera of an edge is its keyframe's (src/Optimizer.cc:664: e->pCamera = pKFi->mpCamera; :690-695: e->fx .. e->bf from
@@ -150,8 +144,8 @@ __device__ __forceinline__ void decide_body(const DevWindow &w, int cur)
         }
         return;
     }
-    F1 = wave_sum(F1);
-    scale = wave_sum(scale);
+    F1 = wave_sum_dpp(F1);
+    scale = wave_sum_dpp(scale);
     if (lane != 0) return;
     scale += scale_pose;
     // g2o on a failed solve: tempChi = DBL_MAX (std::numeric_limits<double>::max(): FINITE), scale = 1e-3, nothing updated.  With a
@@ -502,7 +496,7 @@ __device__ __forceinline__ void point_body(const DevWindow &w, int bid)
         // cost and scale partials of the workgroup behind ONE barrier (the sums in block_reduce's order)
         constexpr int NWV = kPointBlock / 64;
         static_assert(2 * NWV <= kPointRed, "red holds kPointRed doubles (point_lds_bytes)");
-        F = wave_sum(F); scale = wave_sum(scale);
+        F = wave_sum_dpp(F); scale = wave_sum_dpp(scale);
         if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6] = F; red[NWV + (threadIdx.x >> 6)] = scale; }
         __syncthreads();
         // the LM decision needs every workgroup's partials: handed to the pass's deciding wave (decide_body) as two tagged
@@ -539,12 +533,7 @@ __global__ __launch_bounds__(kPointBlock) void k_point_kf(DevWindow w) { point_b
 
 // Batched launches (movba_lba_run_batch): one grid over the concatenated windows; `pre` is the prefix of the windows'
 // block counts for this kernel.  Every window runs exactly the code of its solo launch, so results are bit-identical.
-__device__ __forceinline__ int batch_window(const int32_t *pre, int n, int b)
-{
-    int lo = 0, hi = n - 1;
-    while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (pre[mid] <= b) lo = mid; else hi = mid - 1; }
-    return __builtin_amdgcn_readfirstlane(lo);
-}
+__device__ __forceinline__ int batch_window(const int32_t *pre, int n, int b) { return __builtin_amdgcn_readfirstlane(prefix_find(pre, n, b)); }
 
 template <bool BACKSUB, bool STEREO, bool LDSP>
 __global__ __launch_bounds__(kPointBlock) void k_point_b(BatchDev b)
@@ -564,31 +553,7 @@ __global__ void k_init_pose_b(BatchDev b)
 __device__ __constant__ int8_t kDiagMap[54] = {0, 1, 2, 3, 4, 5, 7, 8, 9, 10, 11, 14, 15, 16, 17, 21, 22, 23, 28, 29, 35, 36, 37, 38, 39, 40, 41, 42, 43, 44, 45, 46, 47, 48, 49, 50, 51, 52, 53, 54, 55, 56, 57, 58, 59, 60, 61, 62, 63, 64, 65, 66, 67, 68};
 __device__ __constant__ int8_t kDiagMirror[21] = {-1, 6, 12, 18, 24, 30, -1, 13, 19, 25, 31, -1, 20, 26, 32, -1, 27, 33, -1, 34, -1};
 
-// Fixed-order reduction of NV per-lane values over the 64 lanes of a wave: two DPP steps sum each quad,
-// the 16 quad sums of every value go through a wave-private LDS strip ([NV][16] doubles) and lane k < NV
-// adds them up in order (returned in lane k).  ~2k cycles for NV = 54, against ~30k for NV butterfly
-// reductions built on ds_bpermute shuffles.
-template <int NV>
-__device__ __forceinline__ double wave_reduce(double (&v)[NV], double *strip, int lane)
-{
-#pragma unroll
-    for (int k = 0; k < NV; ++k) {
-        double t = v[k];
-        t += dpp_mov0<0xb1>(t);
-        t += dpp_mov0<0x4e>(t);
-        if ((lane & 3) == 0) strip[k * 16 + (lane >> 2)] = t;
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    double s = 0.0;
-    if (lane < NV) {
-        const double2 *src = reinterpret_cast<const double2 *>(strip + lane * 16);
-#pragma unroll
-        for (int q = 0; q < 8; ++q) { const double2 t = src[q]; s += t.x; s += t.y; }
-    }
-    return s;                                   // lane k < NV holds the wave's sum of value k
-}
+// (the fixed-order reduction of the sums over a wave: wave_reduce of device_math.h)
 
 // --------------------------------------------------------------------------------
 // k_schur: one workgroup (kSchurWaves waves) per work item (a chunk of up to 2048 of one pose pair's shared points).
@@ -968,7 +933,7 @@ __device__ __forceinline__ void lambda_init_body(const DevWindow &w)
         }
     }
     m = wave_max(m);
-    F = wave_sum(F);
+    F = wave_sum_dpp(F);
     if (lane == 0) {
         c->lambda = 1e-5 * m;
         c->nu = 2.0;

@@ -40,20 +40,6 @@ constexpr int kMargThreads = kStepThreads;      // 4 waves: the nine 16 x 16 MFM
 constexpr int kPointLanes = 8;                  // lanes per map point in k_marg_out
 constexpr int kPointsPerMargBlock = kMargThreads / kPointLanes;
 
-// C + A B^T (NEG = false) or C - A B^T for one wave's 16 x 16 tile (mt, nt) of 48 x 48 LDS images: tile_mfma with a sign
-template <bool NEG>
-__device__ __forceinline__ dbl4 mm_tile(const double *As, const double *Bs, int mt, int nt, int lane, dbl4 c)
-{
-    const double *ap = As + (mt * 16 + (lane & 15)) * LD + (lane >> 4);
-    const double *bp = Bs + (nt * 16 + (lane & 15)) * LD + (lane >> 4);
-    double a[NB / 4], b[NB / 4];
-#pragma unroll
-    for (int q = 0; q < NB / 4; ++q) { a[q] = NEG ? -ap[4 * q] : ap[4 * q]; b[q] = bp[4 * q]; }
-#pragma unroll
-    for (int q = 0; q < NB / 4; ++q) c = __builtin_amdgcn_mfma_f64_16x16x4f64(a[q], b[q], c, 0, 0, 0);
-    return c;
-}
-
 // element r (0..3) of a wave's accumulator u: MFMA tile q = wave + 4 u of the 3 x 3 grid, C/D layout of the instruction
 __device__ __forceinline__ int acc_row(int q, int lane, int r) { return (q / 3) * 16 + (lane >> 4) + 4 * r; }
 __device__ __forceinline__ int acc_col(int q, int lane) { return (q % 3) * 16 + (lane & 15); }
@@ -184,7 +170,7 @@ __global__ __launch_bounds__(kMargThreads) void k_marg_w(MargDev m)
 #pragma unroll
             for (int u = 0; u < 3; ++u) {
                 const int q = wv + 4 * u;
-                if (q < 9) acc[u] = mm_tile<true>(As, Bs, q / 3, q % 3, lane, acc[u]);
+                if (q < 9) acc[u] = tile_mfma<true>(As, Bs, q / 3, q % 3, lane, acc[u]);
             }
         }
         __syncthreads();
@@ -205,7 +191,7 @@ __global__ __launch_bounds__(kMargThreads) void k_marg_w(MargDev m)
         for (int u = 0; u < 3; ++u) {
             const int q = wv + 4 * u;
             if (q < 9) {
-                const dbl4 v = mm_tile<false>(As, Bs, q / 3, q % 3, lane, dzero());
+                const dbl4 v = tile_mfma<false>(As, Bs, q / 3, q % 3, lane, dzero());
                 const int cc = acc_col(q, lane);
                 out[acc_row(q, lane, 0) * NB + cc] = v.x; out[acc_row(q, lane, 1) * NB + cc] = v.y;
                 out[acc_row(q, lane, 2) * NB + cc] = v.z; out[acc_row(q, lane, 3) * NB + cc] = v.w;
@@ -237,7 +223,7 @@ __global__ __launch_bounds__(kMargThreads) void k_marg_sigma(MargDev m)
 #pragma unroll
         for (int u = 0; u < 3; ++u) {
             const int q = wv + 4 * u;
-            if (q < 9) acc[u] = mm_tile<false>(As, Bs, q / 3, q % 3, lane, acc[u]);
+            if (q < 9) acc[u] = tile_mfma<false>(As, Bs, q / 3, q % 3, lane, acc[u]);
         }
     }
     double *out = m.sig + tile_off(I, J);

@@ -747,26 +747,11 @@ __device__ __forceinline__ void pcg_rows_body(const DevWindow &w, const PcgParam
     const DevState &S0 = w.st[cur];
     const DevState &S1 = w.st[cur ^ 1];
     for (int i = tid; i < w.NP; i += kT) {
-        double T[7], Tn[7];
+        double T[7];
 #pragma unroll
         for (int k = 0; k < 7; ++k) T[k] = i == tid ? T0[k] : S0.pose[7 * i + k];
         const int h = i == tid ? h0 : w.hidx[i];
-        if (h >= 0) {
-            double u[6];
-#pragma unroll
-            for (int k = 0; k < 6; ++k) u[k] = p_lds[6 * h + k];
-            se3_oplus(u, T, Tn);
-        } else {
-#pragma unroll
-            for (int k = 0; k < 7; ++k) Tn[k] = T[k];
-        }
-        double R[9];
-        quat_to_R(Tn, R);
-#pragma unroll
-        for (int k = 0; k < 7; ++k) S1.pose[7 * i + k] = Tn[k];
-#pragma unroll
-        for (int k = 0; k < 9; ++k) S1.Rt[12 * i + k] = R[k];
-        S1.Rt[12 * i + 9] = Tn[4]; S1.Rt[12 * i + 10] = Tn[5]; S1.Rt[12 * i + 11] = Tn[6];
+        store_trial_pose(S1.pose, S1.Rt, i, T, h, true, p_lds);
     }
 #ifdef MOVBA_CLOCK_STAMP
     if (ln == 0) for (int k = 0; k < 8; ++k) c->dbg_wseg[wv][k] += seg[k];

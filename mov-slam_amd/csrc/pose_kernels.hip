@@ -23,81 +23,17 @@ namespace {
 constexpr int kT = 256;
 constexpr int kW = kT / 64;
 
+// pose (q, t) -> R row-major, then t
 __device__ __forceinline__ void q2R(const double q[7], double R[12])
 {
-    const double x = q[0], y = q[1], z = q[2], w = q[3];
-    const double tx = 2.0 * x, ty = 2.0 * y, tz = 2.0 * z;
-    const double twx = tx * w, twy = ty * w, twz = tz * w;
-    const double txx = tx * x, txy = ty * x, txz = tz * x;
-    const double tyy = ty * y, tyz = tz * y, tzz = tz * z;
-    R[0] = 1.0 - (tyy + tzz); R[1] = txy - twz;         R[2] = txz + twy;
-    R[3] = txy + twz;         R[4] = 1.0 - (txx + tzz); R[5] = tyz - twx;
-    R[6] = txz - twy;         R[7] = tyz + twx;         R[8] = 1.0 - (txx + tyy);
+    quat_to_R(q, R);
     R[9] = q[4]; R[10] = q[5]; R[11] = q[6];
 }
 
-// (SE3 update and quaternion helpers: device_math.h, shared with the local-BA kernels)
-__device__ __forceinline__ void qnorm(double q[4]) { quat_normalize(q); }
+// (SE3 update, quaternion helpers and the workgroup reduction reduce_all: device_math.h, shared with the local-BA kernels and
+// init_map.hip.  The one wrapper left: called directly, se3_oplus is inlined into k_pose_opt with three sign flips in another
+// order - profiles/device_helpers_isa.md)
 __device__ __forceinline__ void oplus(const double u[6], const double T[7], double out[7]) { se3_oplus(u, T, out); }
-
-// fixed-order reduction of NV values per thread; result in every thread (wave-uniform: scalar registers).  Inside a wave: two
-// DPP steps sum each quad, the 16 quad sums of every value cross a wave-private LDS strip and lane k adds those of value k up in
-// order (a butterfly of 64-bit shuffles per value costs ~500 cycles each: 28 of them were three quarters of an LM iteration);
-// one or two values take the whole-wave DPP tree instead.  Then ONE workgroup barrier: lane k of EVERY wave adds the waves' sums
-// of value k in wave order and the values go round by v_readlane - until round 5 every thread read all kW x NV sums back from
-// LDS itself behind a second barrier (112 eight-byte loads of a lone wave per SIMD: 1 400 of the reduction's 3 600 cycles).
-// The waves' sums alternate between two places (`flip`), so a wave that runs ahead into the next reduction cannot overwrite
-// what a slower one still reads: it stops at that reduction's barrier first.
-constexpr int kRedMax = 28;
-constexpr int kRedLds = 2 * kW * kRedMax + kW * kRedMax * 16;
-template <int NV>
-__device__ __forceinline__ void reduce_all(double (&v)[NV], double *lds /* kRedLds */, int &flip)
-{
-    static_assert(NV <= kRedMax, "reduce_all: LDS strips sized for 28 values");
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    double *cross = lds + flip * (kW * kRedMax);
-    flip ^= 1;
-    if (NV <= 2) {
-#pragma unroll
-        for (int k = 0; k < NV; ++k) {
-            const double t = wave_sum_dpp(v[k]);
-            if (lane == 0) cross[wave * NV + k] = t;
-        }
-    } else {
-        double *strip = lds + 2 * kW * kRedMax + wave * (NV * 16);
-#pragma unroll
-        for (int k = 0; k < NV; ++k) {
-            double t = v[k];
-            t += dpp_mov0<0xb1>(t);
-            t += dpp_mov0<0x4e>(t);
-            if ((lane & 3) == 0) strip[k * 16 + (lane >> 2)] = t;
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        if (lane < NV) {
-            const double2 *src = reinterpret_cast<const double2 *>(strip + lane * 16);
-            double2 t[8];
-#pragma unroll
-            for (int q = 0; q < 8; ++q) t[q] = src[q];
-            double s = 0.0;
-#pragma unroll
-            for (int q = 0; q < 8; ++q) { s += t[q].x; s += t[q].y; }
-            cross[wave * NV + lane] = s;
-        }
-    }
-    __syncthreads();
-    const int kk = lane < NV ? lane : NV - 1;
-    double w[kW];
-#pragma unroll
-    for (int q = 0; q < kW; ++q) w[q] = cross[q * NV + kk];
-    double tot = w[0];
-#pragma unroll
-    for (int q = 1; q < kW; ++q) tot += w[q];
-#pragma unroll
-    for (int k = 0; k < NV; ++k) v[k] = readlane_f64(tot, k);
-}
-
 // (dense 6x6 LL^T solve: solve6 of device_math.h, shared with the two-keyframe bundle adjustment of init_map.hip)
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -233,7 +169,8 @@ __device__ int p3p_grunert(const double X[3][3], const double j[3][3], double Rs
     return ns;
 }
 
-// rotation matrix (row-major) -> unit quaternion (x, y, z, w), w >= 0 (Eigen's conversion, as in oplus above)
+// rotation matrix (row-major) -> unit quaternion (x, y, z, w), w >= 0 (Eigen's conversion, as in se3_oplus)
+// (kept apart from device_math.h's R_to_quat: sqrt and a division here, rsqrt there, and a normalisation behind - other bits)
 __device__ void R2q(const double m[9], double q[4])
 {
     double t = m[0] + m[4] + m[8];
@@ -250,7 +187,7 @@ __device__ void R2q(const double m[9], double q[4])
         t = sqrt(m[8] - m[0] - m[4] + 1.0); q[2] = 0.5 * t; t = 0.5 / t;
         q[3] = (m[3] - m[1]) * t; q[0] = (m[2] + m[6]) * t; q[1] = (m[5] + m[7]) * t;
     }
-    qnorm(q);
+    quat_normalize(q);
 }
 
 }  // namespace
@@ -338,7 +275,7 @@ __global__ __launch_bounds__(kT) void k_pose_hyp(PoseDev p) { pose_hyp_body(p, b
 __global__ __launch_bounds__(kT) void k_pose_hyp_b(const PoseDev *__restrict__ frames, const int32_t *__restrict__ hyp_first, int nf)
 {
     const int b = blockIdx.x;
-    int lo = 0, hi = nf - 1;
+    int lo = 0, hi = nf - 1;                // (prefix_find of device_math.h written out: through the call one scalar add swaps its operands)
     while (lo < hi) {
         const int mid = (lo + hi + 1) >> 1;
         if (hyp_first[mid] <= b) lo = mid; else hi = mid - 1;
@@ -353,7 +290,7 @@ __global__ __launch_bounds__(kT) void k_pose_hyp_b(const PoseDev *__restrict__ f
 template <bool STAGED>
 __device__ __forceinline__ void pose_opt_body(const PoseDev &p)
 {
-    __shared__ __attribute__((aligned(16))) double lds[kRedLds];      // reduce_all: the waves' sums (two places), then a strip per wave
+    __shared__ __attribute__((aligned(16))) double lds[kRedLds<kW>];      // reduce_all: the waves' sums (two places), then a strip per wave
     int flip = 0;
     extern __shared__ __attribute__((aligned(16))) double dyn[];
     const int tid = threadIdx.x;
@@ -483,7 +420,7 @@ __device__ __forceinline__ void pose_opt_body(const PoseDev &p)
                 F[0] += (robust && p.huber_delta > 0.0 && !(chi2 <= dsqr)) ? 2.0 * sqrt(chi2) * p.huber_delta - dsqr : chi2;
             }
         }
-        reduce_all<1>(F, lds, flip);
+        reduce_all<kW>(F, lds, flip);
         return F[0];
     };
 
@@ -500,7 +437,7 @@ __device__ __forceinline__ void pose_opt_body(const PoseDev &p)
     auto lm_round = [&](bool robust, int its) {
         double cnt[1] = { 0.0 };
         for (int i = tid; i < p.n; i += kT) cnt[0] += level1[i] ? 0.0 : 1.0;
-        reduce_all<1>(cnt, lds, flip);
+        reduce_all<kW>(cnt, lds, flip);
         bool ok = cnt[0] > 0.0;
         double lambda = 0.0, ni = 2.0;
         for (int it = 0; it < its && ok; ++it) {
@@ -559,7 +496,7 @@ __device__ __forceinline__ void pose_opt_body(const PoseDev &p)
               }
             }
             POSE_STAMP(0);
-            reduce_all<28>(acc, lds, flip);
+            reduce_all<kW>(acc, lds, flip);
             POSE_STAMP(1);
             double F0 = acc[27];
             if (it == 0) {
@@ -625,7 +562,7 @@ __device__ __forceinline__ void pose_opt_body(const PoseDev &p)
             sc[0] += in ? 1.0 : 0.0; sc[1] += ls;
             if (mark) { level1[i] = in ? 0 : 1; wls[i] = wt; }
         }
-        reduce_all<2>(sc, lds, flip);
+        reduce_all<kW>(sc, lds, flip);
         cnt_o = sc[0]; cst_o = sc[1];
     };
     // ---- local optimisation of the winning hypothesis (USAC's LO step; MAGSAC++'s model polishing is iteratively reweighted least
@@ -677,7 +614,7 @@ __device__ __forceinline__ void pose_opt_body(const PoseDev &p)
             level1[i] = (uint8_t)bad;
             nb[0] += bad;
         }
-        reduce_all<1>(nb, lds, flip);
+        reduce_all<kW>(nb, lds, flip);
         n_bad = (int)nb[0];
         if (p.n - n_bad < 10) break;
     }

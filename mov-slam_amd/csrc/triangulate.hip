@@ -7,23 +7,13 @@
 // broadcast).  No atomics, no reductions: a match's result is written by its own thread and depends on nothing else.
 #include <hip/hip_runtime.h>
 
+#include "device_math.h"
 #include "triangulate.h"
 #include "triangulate_math.h"
 
 namespace movba {
 
 namespace {
-
-// the pair of match m: the largest p with pair_ptr[p] <= m (pair_ptr[n_pairs] = n_matches > m: empty pairs are never found)
-__device__ __forceinline__ int tri_pair_of(const int32_t *__restrict__ pair_ptr, int n_pairs, int m)
-{
-    int lo = 0, hi = n_pairs - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (pair_ptr[mid] <= m) lo = mid; else hi = mid - 1;
-    }
-    return lo;
-}
 
 __global__ __launch_bounds__(kTriThreads) void k_triangulate(const TriDev d)
 {
@@ -34,8 +24,8 @@ __global__ __launch_bounds__(kTriThreads) void k_triangulate(const TriDev d)
     const int m = m0 + tid;
     const bool live = m < n;
     const int m_last = min(m0 + kTriThreads - 1, n - 1);
-    const int p_lo = tri_pair_of(d.pair_ptr, d.n_pairs, m0), p_hi = tri_pair_of(d.pair_ptr, d.n_pairs, m_last);
-    const int p = live ? tri_pair_of(d.pair_ptr, d.n_pairs, m) : -1;
+    const int p_lo = prefix_find(d.pair_ptr, d.n_pairs, m0), p_hi = prefix_find(d.pair_ptr, d.n_pairs, m_last);
+    const int p = live ? prefix_find(d.pair_ptr, d.n_pairs, m) : -1;
 
     double u1 = 0.0, w1 = 0.0, u2 = 0.0, w2 = 0.0, ur1 = -1.0, ur2 = -1.0, d1 = 0.0, d2 = 0.0;
     if (live) {

@@ -17,6 +17,7 @@
 // No atomics on floating-point data: sums are per-lane partial sums combined by a butterfly in a fixed order; counts are integers.
 #include <hip/hip_runtime.h>
 
+#include "device_math.h"
 #include "two_view.h"
 #include "two_view_math.h"
 
@@ -25,16 +26,6 @@ namespace movba {
 namespace {
 
 struct TvSyncWg { __device__ void operator()() const { __syncthreads(); } };
-
-__device__ __forceinline__ int tv_pair_of(const int32_t *__restrict__ first, int n_pairs, int b)
-{
-    int lo = 0, hi = n_pairs - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (first[mid] <= b) lo = mid; else hi = mid - 1;
-    }
-    return lo;
-}
 
 __device__ __forceinline__ int wave_sum(int v)
 {
@@ -49,7 +40,7 @@ __global__ __launch_bounds__(kTvThreads) void k_tv_hyp(const TvDev d)
     __shared__ double q[20], E[9 * kTvMaxSol];
     __shared__ int nsol_s;
     const int tid = threadIdx.x;
-    const int pi = tv_pair_of(d.hyp_first, d.n_pairs, blockIdx.x);
+    const int pi = prefix_find(d.hyp_first, d.n_pairs, blockIdx.x);
     const TvPair p = d.pairs[pi];
     const int h = blockIdx.x - d.hyp_first[pi];
     const size_t hg = (size_t)p.h0 + h;

@@ -763,6 +763,7 @@ __host__ __device__ inline void tv_lo_result(const TvLoTrack &tr, double *E)
 }
 
 // rotation matrix (row-major) -> unit quaternion (x, y, z, w) (Eigen's conversion)
+// (its own copy: host and device, compared bit for bit by the CPU drivers; device_math.h's R_to_quat and pose_kernels.hip's R2q round otherwise)
 __host__ __device__ inline void tv_R2q(const double *m, double *q)
 {
     double t = m[0] + m[4] + m[8];
