@@ -134,11 +134,25 @@ struct Scratch {
 MOVBA_INTERNAL int ensure_arena(movba_handle *h, size_t bytes);
 MOVBA_INTERNAL int ensure_stage(movba_handle *h, size_t bytes);
 // The front of every call that borrows the staging buffer and the pose scratch beside the LBA calls (movba_pose_opt,
-// movba_pose_opt_batch, movba_triangulate, movba_two_view): the device is set, the pose scratch holds dev_bytes (0: the call
-// needs no device copy) and the staging buffer stage_bytes, and nothing of an earlier call or upload is still using either.
+// movba_pose_opt_batch, movba_triangulate, the front of movba_two_view / movba_two_view_lo, movba_init_map, movba_view_points,
+// movba_point_normals, movba_lba_point_normals): the device is set, the pose scratch holds dev_bytes (0: the call needs no
+// device copy yet) and the staging buffer stage_bytes, and nothing of an earlier call or upload is still using either.
 MOVBA_INTERNAL int begin_side_call(movba_handle *h, size_t dev_bytes, size_t stage_bytes);
 // device view of [p, p + bytes) if it lies inside a movba_host_alloc block, else nullptr
 MOVBA_INTERNAL unsigned long long *host_block_view(const void *p, size_t bytes);
+
+// typed view of the bytes at `off` of a buffer (device-only scratch, the side calls' fixed-size records)
+template <typename T> T *at(char *base, size_t off) { return reinterpret_cast<T *>(base + off); }
+
+// One input array of a side call: `count` elements in the staging buffer, mirrored into the pose scratch by the call's one H2D
+// copy.  An optional array that is absent is plan(0, c): the layout stays where it is, fill copies nothing, `dev` is nullptr.
+template <typename T> struct In {
+    size_t off = 0, count = 0;
+    void plan(size_t n, Carver &c) { count = n; off = c.take<T>(n); }
+    T *host(char *stage) const { return at<T>(stage, off); }   // (inputs the host computes in place)
+    void fill(char *stage, const T *src) const { if (count) std::memcpy(stage + off, src, sizeof(T) * count); }
+    const T *dev(char *arena) const { return count ? at<T>(arena, off) : nullptr; }
+};
 
 // One result array of the caller: written by the kernels where it lies (movba_host_alloc memory), or into the staging buffer
 // and copied out behind the synchronisation; `dev` stays nullptr for an array the caller left out.
@@ -154,7 +168,17 @@ template <typename T> struct Out {
         staged = !dev;
         if (staged) off = c.take<T>(n);
     }
-    void bind(char *stage_dev) { if (staged) dev = reinterpret_cast<T *>(stage_dev + off); }
+    // one pair's array: elements [first, first + n) of what the call carved for all pairs at base_off, unless it lies in
+    // movba_host_alloc memory (a pair the kernels skip, n == 0, keeps its empty slice)
+    void plan_within(T *p, size_t n, size_t base_off, size_t first)
+    {
+        user = p; count = n;
+        if (!p) return;
+        if (n) dev = reinterpret_cast<T *>(host_block_view(p, sizeof(T) * n));
+        staged = !dev;
+        off = base_off + sizeof(T) * first;
+    }
+    void bind(char *stage_dev) { if (staged) dev = at<T>(stage_dev, off); }
     void fetch(const char *stage) const { if (staged) std::memcpy(user, stage + off, sizeof(T) * count); }
 };
 

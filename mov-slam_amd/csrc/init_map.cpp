@@ -4,6 +4,7 @@
 // up as ones), sends them with ONE copy, queues the launch and hands the results over after ONE synchronisation.  `points` and
 // `chi2` that lie in movba_host_alloc memory are written by the kernel itself; others arrive in the staging buffer and are
 // copied out.  A pair without a used match never reaches the device: its result is filled in here.
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <limits>
@@ -62,9 +63,12 @@ extern "C" int movba_init_map(movba_handle *h, const movba_init_map_desc *descs,
     // arrays.  The scratch behind the inputs on the device is sized by the used matches, which are only known once the masks
     // are staged: the staging buffer is laid out (and grown) first, the device arena after the count.
     Carver c;
-    const size_t o_pairs = c.take<ImPair>(np);
-    const size_t o_obs1 = c.take<double>(2 * M), o_obs2 = c.take<double>(2 * M), o_pts = c.take<double>(3 * M);
-    const size_t o_sig1 = c.take<double>(M), o_sig2 = c.take<double>(M), o_use = c.take<uint8_t>(M);
+    In<ImPair> in_pairs;
+    In<double> obs1, obs2, pts, sig1, sig2;
+    In<uint8_t> mask;
+    in_pairs.plan(np, c);
+    obs1.plan(2 * M, c); obs2.plan(2 * M, c); pts.plan(3 * M, c);
+    sig1.plan(M, c); sig2.plan(M, c); mask.plan(M, c);
     const size_t h2d = c.off;
     Carver dv = c;
     const size_t o_out = c.take<double>(kImOutDoubles * np);
@@ -75,10 +79,10 @@ extern "C" int movba_init_map(movba_handle *h, const movba_init_map_desc *descs,
     for (int j = 0; j < n; ++j) results[j].status = MOVBA_ERR_HIP;      // (until the device work is through)
     int rc = begin_side_call(h, 0, total); if (rc) return rc;
 
-    char *sg = h->stage;
+    char *sg = h->stage, *sd = h->stage_dev;
     std::vector<ImPair> pairs(np);
-    struct View { unsigned long long *pts, *chi; };
-    std::vector<View> views(np);
+    struct PairOut { Out<double> pts, chi; };       // each pair's share of the per-match results
+    std::vector<PairOut> outs(np);
     size_t m_at = 0, U = 0;
     for (int k = 0; k < n; ++k) {
         const movba_init_map_desc &d = descs[k];
@@ -86,15 +90,15 @@ extern "C" int movba_init_map(movba_handle *h, const movba_init_map_desc *descs,
         ImPair &p = pairs[k];
         std::memset(&p, 0, sizeof p);
         const size_t m = (size_t)d.n_matches;
-        uint8_t *use = reinterpret_cast<uint8_t *>(sg + o_use) + m_at;
+        uint8_t *use = mask.host(sg) + m_at;
         if (m) {
-            std::memcpy(sg + o_obs1 + sizeof(double) * 2 * m_at, d.obs1, sizeof(double) * 2 * m);
-            std::memcpy(sg + o_obs2 + sizeof(double) * 2 * m_at, d.obs2, sizeof(double) * 2 * m);
-            std::memcpy(sg + o_pts + sizeof(double) * 3 * m_at, d.points, sizeof(double) * 3 * m);
-            double *s1 = reinterpret_cast<double *>(sg + o_sig1) + m_at, *s2 = reinterpret_cast<double *>(sg + o_sig2) + m_at;
-            if (d.inv_sigma2_1) std::memcpy(s1, d.inv_sigma2_1, sizeof(double) * m); else std::fill(s1, s1 + m, 1.0);
-            if (d.inv_sigma2_2) std::memcpy(s2, d.inv_sigma2_2, sizeof(double) * m); else std::fill(s2, s2 + m, 1.0);
-            if (d.use) std::memcpy(use, d.use, m); else std::memset(use, 1, m);
+            std::copy_n(d.obs1, 2 * m, obs1.host(sg) + 2 * m_at);
+            std::copy_n(d.obs2, 2 * m, obs2.host(sg) + 2 * m_at);
+            std::copy_n(d.points, 3 * m, pts.host(sg) + 3 * m_at);
+            double *s1 = sig1.host(sg) + m_at, *s2 = sig2.host(sg) + m_at;
+            if (d.inv_sigma2_1) std::copy_n(d.inv_sigma2_1, m, s1); else std::fill_n(s1, m, 1.0);
+            if (d.inv_sigma2_2) std::copy_n(d.inv_sigma2_2, m, s2); else std::fill_n(s2, m, 1.0);
+            if (d.use) std::copy_n(d.use, m, use); else std::fill_n(use, m, uint8_t(1));
         }
         // (counted in the staged copy, which is what the kernel compacts: a caller that changes its mask meanwhile cannot make
         // the two disagree)
@@ -104,16 +108,15 @@ extern "C" int movba_init_map(movba_handle *h, const movba_init_map_desc *descs,
         p.max_iters = d.max_iters; p.max_trials = d.max_trials; p.min_tracked = d.min_tracked;
         for (int e = 0; e < 7; ++e) p.pose2[e] = d.pose2[e];
         p.fx = d.fx; p.fy = d.fy; p.cx = d.cx; p.cy = d.cy; p.huber = d.huber_delta;
-        View &v = views[k];
-        v.pts = used ? host_block_view(r.points, sizeof(double) * 3 * m) : nullptr;
-        v.chi = used && r.chi2 ? host_block_view(r.chi2, sizeof(double) * 2 * m) : nullptr;
-        p.points = v.pts ? reinterpret_cast<double *>(v.pts) : reinterpret_cast<double *>(h->stage_dev + o_rpts) + 3 * m_at;
-        p.chi2 = !r.chi2 ? nullptr : v.chi ? reinterpret_cast<double *>(v.chi) : reinterpret_cast<double *>(h->stage_dev + o_rchi) + 2 * m_at;
-        p.out = reinterpret_cast<double *>(h->stage_dev + o_out) + (size_t)kImOutDoubles * k;
-        p.trace = trace ? reinterpret_cast<double *>(h->stage_dev + o_trace) + (size_t)kImTraceDoubles * k : nullptr;
+        PairOut &v = outs[k];
+        v.pts.plan_within(r.points, used ? 3 * m : 0, o_rpts, 3 * m_at); v.chi.plan_within(r.chi2, used ? 2 * m : 0, o_rchi, 2 * m_at);
+        v.pts.bind(sd); v.chi.bind(sd);
+        p.points = v.pts.dev; p.chi2 = v.chi.dev;       // (chi2 left out: nullptr, and the kernel skips it)
+        p.out = at<double>(sd, o_out) + (size_t)kImOutDoubles * k;
+        p.trace = trace ? at<double>(sd, o_trace) + (size_t)kImTraceDoubles * k : nullptr;
         m_at += m; U += used;
     }
-    std::memcpy(sg + o_pairs, pairs.data(), sizeof(ImPair) * np);
+    in_pairs.fill(sg, pairs.data());
 
     if (U) {
         const size_t o_idx = dv.take<int32_t>(U), o_X = dv.take<double>(3 * U), o_Xbk = dv.take<double>(3 * U);
@@ -123,13 +126,11 @@ extern "C" int movba_init_map(movba_handle *h, const movba_init_map_desc *descs,
         char *ar = h->pose_scratch.p;
         ImDev t{};
         t.n_pairs = n;
-        t.pairs = reinterpret_cast<const ImPair *>(ar + o_pairs);
-        t.obs1 = reinterpret_cast<const double *>(ar + o_obs1); t.obs2 = reinterpret_cast<const double *>(ar + o_obs2);
-        t.pts = reinterpret_cast<const double *>(ar + o_pts);
-        t.sig1 = reinterpret_cast<const double *>(ar + o_sig1); t.sig2 = reinterpret_cast<const double *>(ar + o_sig2);
-        t.use = reinterpret_cast<const uint8_t *>(ar + o_use);
-        t.idx = reinterpret_cast<int32_t *>(ar + o_idx); t.X = reinterpret_cast<double *>(ar + o_X);
-        t.Xbk = reinterpret_cast<double *>(ar + o_Xbk); t.lin = reinterpret_cast<double *>(ar + o_lin);
+        t.pairs = in_pairs.dev(ar);
+        t.obs1 = obs1.dev(ar); t.obs2 = obs2.dev(ar); t.pts = pts.dev(ar);
+        t.sig1 = sig1.dev(ar); t.sig2 = sig2.dev(ar); t.use = mask.dev(ar);
+        t.idx = at<int32_t>(ar, o_idx); t.X = at<double>(ar, o_X);
+        t.Xbk = at<double>(ar, o_Xbk); t.lin = at<double>(ar, o_lin);
         HIP_TRY(hipMemcpyAsync(ar, sg, h2d, hipMemcpyHostToDevice, h->stream));
         HIP_TRY(launch_init_map(t, h->stream));
         HIP_TRY(hipStreamSynchronize(h->stream));
@@ -148,16 +149,14 @@ extern "C" int movba_init_map(movba_handle *h, const movba_init_map_desc *descs,
             if (tr) tr->n_trace = tr->pad = 0;
             continue;
         }
-        const size_t m = (size_t)p.n, at = (size_t)p.m0;
-        if (!views[k].pts) std::memcpy(r.points, sg + o_rpts + sizeof(double) * 3 * at, sizeof(double) * 3 * m);
-        if (r.chi2 && !views[k].chi) std::memcpy(r.chi2, sg + o_rchi + sizeof(double) * 2 * at, sizeof(double) * 2 * m);
-        const double *o = reinterpret_cast<const double *>(sg + o_out) + (size_t)kImOutDoubles * k;
+        outs[k].pts.fetch(sg); outs[k].chi.fetch(sg);
+        const double *o = at<const double>(sg, o_out) + (size_t)kImOutDoubles * k;
         for (int e = 0; e < 7; ++e) r.pose[e] = o[e];
         r.median_depth = o[7]; r.outcome = (int32_t)o[8]; r.n_used = (int32_t)o[9]; r.iters_done = (int32_t)o[10];
         r.n_solves = (int32_t)o[11]; r.last_rejected = (int32_t)o[12]; r.n_chol_fail = (int32_t)o[13];
         r.lambda = o[14]; r.cost0 = o[15]; r.cost = o[16]; r.pad = 0;
         if (tr) {
-            const double *t = reinterpret_cast<const double *>(sg + o_trace) + (size_t)kImTraceDoubles * k;
+            const double *t = at<const double>(sg, o_trace) + (size_t)kImTraceDoubles * k;
             const int nt = (int)t[0];
             tr->n_trace = nt; tr->pad = 0;
             for (int e = 0; e < nt; ++e) {

@@ -16,11 +16,6 @@ namespace {
 
 constexpr int32_t kPnMaxObs = 1 << 28;
 
-template <typename T> void put(char *stage, size_t off, const T *src, size_t count)
-{
-    std::memcpy(stage + off, src, sizeof(T) * count);
-}
-
 // n_levels, the table and every point's octave: what both entry points take as they are
 bool pn_levels_ok(int32_t n_levels, const double *scale, const int32_t *ref_level, size_t np)
 {
@@ -96,10 +91,12 @@ int movba_point_normals(movba_handle *h, const movba_normals_desc *desc, movba_n
     }
 
     // Layout.  [0, h2d): the inputs, one H2D copy into the handle's side-call scratch.  Behind them on the device: the views'
-    // centres; behind them in the staging buffer: the results that do not go straight into the caller's pinned arrays.
+    // centres; behind them in the staging buffer: the results (Out: those that are staged).
     Carver c;
-    const size_t o_poses = c.take<double>(7 * nv), o_pts = c.take<double>(3 * np), o_ptr = c.take<int32_t>(np + 1);
-    const size_t o_view = c.take<int32_t>(n_obs), o_rv = c.take<int32_t>(np), o_rl = c.take<int32_t>(np), o_scale = c.take<double>(nl);
+    In<double> poses, pts, scale;
+    In<int32_t> ptr, view, rv, rl;
+    poses.plan(7 * nv, c); pts.plan(3 * np, c); ptr.plan(np + 1, c);
+    view.plan(n_obs, c); rv.plan(np, c); rl.plan(np, c); scale.plan(nl, c);
     const size_t h2d = c.off;
     Carver dv = c;
     const size_t o_ctr = dv.take<double>(3 * nv);
@@ -111,17 +108,14 @@ int movba_point_normals(movba_handle *h, const movba_normals_desc *desc, movba_n
     int rc = begin_side_call(h, dv.off, total); if (rc) return rc;
 
     char *sg = h->stage, *ar = h->pose_scratch.p;
-    put(sg, o_poses, d.poses, 7 * nv); put(sg, o_pts, d.points, 3 * np); put(sg, o_ptr, d.obs_ptr, np + 1);
-    put(sg, o_view, d.obs_view, n_obs); put(sg, o_rv, d.ref_view, np); put(sg, o_rl, d.ref_level, np);
-    put(sg, o_scale, d.scale_factors, nl);
+    poses.fill(sg, d.poses); pts.fill(sg, d.points); ptr.fill(sg, d.obs_ptr);
+    view.fill(sg, d.obs_view); rv.fill(sg, d.ref_view); rl.fill(sg, d.ref_level); scale.fill(sg, d.scale_factors);
 
     PnDev t{};
     t.n_views = d.n_views; t.n_points = d.n_points; t.n_levels = d.n_levels;
-    t.poses = reinterpret_cast<const double *>(ar + o_poses); t.points = reinterpret_cast<const double *>(ar + o_pts);
-    t.lists.ptr = reinterpret_cast<const int32_t *>(ar + o_ptr); t.lists.view = reinterpret_cast<const int32_t *>(ar + o_view);
-    t.ref_view = reinterpret_cast<const int32_t *>(ar + o_rv); t.ref_level = reinterpret_cast<const int32_t *>(ar + o_rl);
-    t.scale = reinterpret_cast<const double *>(ar + o_scale);
-    t.centres = reinterpret_cast<double *>(ar + o_ctr);
+    t.poses = poses.dev(ar); t.points = pts.dev(ar); t.lists.ptr = ptr.dev(ar); t.lists.view = view.dev(ar);
+    t.ref_view = rv.dev(ar); t.ref_level = rl.dev(ar); t.scale = scale.dev(ar);
+    t.centres = at<double>(ar, o_ctr);
     out.bind(h->stage_dev, t);
 
     HIP_TRY(hipMemcpyAsync(ar, sg, h2d, hipMemcpyHostToDevice, h->stream));
@@ -151,8 +145,10 @@ int movba_lba_point_normals(movba_handle *h, const int32_t *ref_pose, const int3
     // Layout as above; what crosses the bus is the reference entries, the table and the caller's flags - never read through
     // DevWindow::out_outlier, and not through a pointer the window kept from an earlier call.
     Carver c;
-    const size_t o_rv = c.take<int32_t>(np), o_rl = c.take<int32_t>(np), o_scale = c.take<double>(nl);
-    const size_t o_mask = outlier ? c.take<uint8_t>(ne) : 0;
+    In<int32_t> rv, rl;
+    In<double> scale;
+    In<uint8_t> mask;
+    rv.plan(np, c); rl.plan(np, c); scale.plan(nl, c); mask.plan(outlier ? ne : 0, c);
     const size_t h2d = c.off;
     Carver dv = c;
     const size_t o_ctr = dv.take<double>(3 * nv);
@@ -163,18 +159,16 @@ int movba_lba_point_normals(movba_handle *h, const int32_t *ref_pose, const int3
     int rc = begin_side_call(h, dv.off, total); if (rc) return rc;
 
     char *sg = h->stage, *ar = h->pose_scratch.p;
-    put(sg, o_rv, ref_pose, np); put(sg, o_rl, ref_level, np); put(sg, o_scale, scale_factors, nl);
-    if (outlier) put(sg, o_mask, outlier, ne);
+    rv.fill(sg, ref_pose); rl.fill(sg, ref_level); scale.fill(sg, scale_factors); mask.fill(sg, outlier);
 
     PnDev t{};
     t.n_views = w.NP; t.n_points = w.P; t.n_levels = n_levels;
     t.cur = &w.ctrl->cur;               // (an address on the device: read there, as k_export reads it)
     for (int k = 0; k < 2; ++k) { t.pose_st[k] = w.st[k].pose; t.point_st[k] = w.st[k].point; }
     t.lists.ptr = w.pt_start; t.lists.view = w.g_pose; t.lists.perm = w.perm;
-    t.lists.mask = outlier ? reinterpret_cast<const uint8_t *>(ar + o_mask) : nullptr;
-    t.ref_view = reinterpret_cast<const int32_t *>(ar + o_rv); t.ref_level = reinterpret_cast<const int32_t *>(ar + o_rl);
-    t.scale = reinterpret_cast<const double *>(ar + o_scale);
-    t.centres = reinterpret_cast<double *>(ar + o_ctr);
+    t.lists.mask = mask.dev(ar);
+    t.ref_view = rv.dev(ar); t.ref_level = rl.dev(ar); t.scale = scale.dev(ar);
+    t.centres = at<double>(ar, o_ctr);
     out.bind(h->stage_dev, t);
 
     HIP_TRY(hipMemcpyAsync(ar, sg, h2d, hipMemcpyHostToDevice, h->stream));

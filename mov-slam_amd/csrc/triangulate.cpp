@@ -36,11 +36,6 @@ bool tri_desc_ok(const movba_tri_desc &d, const movba_tri_result &r)
     return true;
 }
 
-template <typename T> void put(char *stage, size_t off, const T *src, size_t count)
-{
-    std::memcpy(stage + off, src, sizeof(T) * count);
-}
-
 }  // namespace
 
 extern "C" int movba_triangulate(movba_handle *h, const movba_tri_desc *desc, movba_tri_result *res)
@@ -53,51 +48,41 @@ extern "C" int movba_triangulate(movba_handle *h, const movba_tri_desc *desc, mo
     const size_t nv = (size_t)d.n_views, np = (size_t)d.n_pairs;
     const bool stereo_views = d.bf && d.b;
 
-    // Layout.  [0, h2d): the inputs, one H2D copy into the handle's pose scratch; behind them (staging buffer only) the
-    // results that do not go straight into the caller's pinned arrays.
+    // Layout.  [0, h2d): the inputs; behind them (staging buffer only) the results.
     Carver c;
-    const size_t o_poses = c.take<double>(7 * nv), o_cam = c.take<double>(4 * nv);
-    const size_t o_bf = stereo_views ? c.take<double>(nv) : 0, o_b = stereo_views ? c.take<double>(nv) : 0;
-    const size_t o_pv = c.take<int32_t>(2 * np), o_pp = c.take<int32_t>(np + 1);
-    const size_t o_obs1 = c.take<double>(2 * n), o_obs2 = c.take<double>(2 * n);
-    const size_t o_ur1 = d.ur1 ? c.take<double>(n) : 0, o_d1 = d.ur1 ? c.take<double>(n) : 0;
-    const size_t o_ur2 = d.ur2 ? c.take<double>(n) : 0, o_d2 = d.ur2 ? c.take<double>(n) : 0;
+    In<double> poses, cam, bf, b, obs1, obs2, ur1, d1, ur2, d2;
+    In<int32_t> pv, pp;
+    poses.plan(7 * nv, c); cam.plan(4 * nv, c); bf.plan(stereo_views ? nv : 0, c); b.plan(stereo_views ? nv : 0, c);
+    pv.plan(2 * np, c); pp.plan(np + 1, c); obs1.plan(2 * n, c); obs2.plan(2 * n, c);
+    ur1.plan(d.ur1 ? n : 0, c); d1.plan(d.ur1 ? n : 0, c); ur2.plan(d.ur2 ? n : 0, c); d2.plan(d.ur2 ? n : 0, c);
     const size_t h2d = c.off;
-    unsigned long long *user_points = host_block_view(res->points, sizeof(double) * 3 * n);
-    unsigned long long *user_code = host_block_view(res->code, n);
-    const size_t o_points = user_points ? 0 : c.take<double>(3 * n), o_code = user_code ? 0 : c.take<uint8_t>(n);
+    Out<double> points;
+    Out<uint8_t> code;
+    points.plan(res->points, 3 * n, c); code.plan(res->code, n, c);
     const size_t total = c.off;
 
     res->status = MOVBA_ERR_HIP;            // (until the device work is through)
     int rc = begin_side_call(h, h2d, total); if (rc) return rc;
 
     char *sg = h->stage, *ar = h->pose_scratch.p;
-    put(sg, o_poses, d.poses, 7 * nv); put(sg, o_cam, d.cam, 4 * nv);
-    if (stereo_views) { put(sg, o_bf, d.bf, nv); put(sg, o_b, d.b, nv); }
-    put(sg, o_pv, d.pair_view, 2 * np); put(sg, o_pp, d.pair_ptr, np + 1);
-    put(sg, o_obs1, d.obs1, 2 * n); put(sg, o_obs2, d.obs2, 2 * n);
-    if (d.ur1) { put(sg, o_ur1, d.ur1, n); put(sg, o_d1, d.depth1, n); }
-    if (d.ur2) { put(sg, o_ur2, d.ur2, n); put(sg, o_d2, d.depth2, n); }
+    poses.fill(sg, d.poses); cam.fill(sg, d.cam); bf.fill(sg, d.bf); b.fill(sg, d.b);
+    pv.fill(sg, d.pair_view); pp.fill(sg, d.pair_ptr); obs1.fill(sg, d.obs1); obs2.fill(sg, d.obs2);
+    ur1.fill(sg, d.ur1); d1.fill(sg, d.depth1); ur2.fill(sg, d.ur2); d2.fill(sg, d.depth2);
 
-    auto dbl = [&](size_t off) { return reinterpret_cast<const double *>(ar + off); };
     TriDev t{};
     t.n_matches = (int32_t)n; t.n_pairs = d.n_pairs;
-    t.poses = dbl(o_poses); t.cam = dbl(o_cam);
-    t.bf = stereo_views ? dbl(o_bf) : nullptr; t.b = stereo_views ? dbl(o_b) : nullptr;
-    t.pair_view = reinterpret_cast<const int32_t *>(ar + o_pv); t.pair_ptr = reinterpret_cast<const int32_t *>(ar + o_pp);
-    t.obs1 = dbl(o_obs1); t.obs2 = dbl(o_obs2);
-    t.ur1 = d.ur1 ? dbl(o_ur1) : nullptr; t.depth1 = d.ur1 ? dbl(o_d1) : nullptr;
-    t.ur2 = d.ur2 ? dbl(o_ur2) : nullptr; t.depth2 = d.ur2 ? dbl(o_d2) : nullptr;
+    t.poses = poses.dev(ar); t.cam = cam.dev(ar); t.bf = bf.dev(ar); t.b = b.dev(ar);
+    t.pair_view = pv.dev(ar); t.pair_ptr = pp.dev(ar); t.obs1 = obs1.dev(ar); t.obs2 = obs2.dev(ar);
+    t.ur1 = ur1.dev(ar); t.depth1 = d1.dev(ar); t.ur2 = ur2.dev(ar); t.depth2 = d2.dev(ar);
     t.gate = d.reproj_gate; t.far_th = d.far_threshold;
-    t.points = user_points ? reinterpret_cast<double *>(user_points) : reinterpret_cast<double *>(h->stage_dev + o_points);
-    t.code = user_code ? reinterpret_cast<uint8_t *>(user_code) : reinterpret_cast<uint8_t *>(h->stage_dev + o_code);
+    points.bind(h->stage_dev); code.bind(h->stage_dev);
+    t.points = points.dev; t.code = code.dev;
 
     HIP_TRY(hipMemcpyAsync(ar, sg, h2d, hipMemcpyHostToDevice, h->stream));
     HIP_TRY(launch_triangulate(t, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
 
-    if (!user_points) std::memcpy(res->points, sg + o_points, sizeof(double) * 3 * n);
-    if (!user_code) std::memcpy(res->code, sg + o_code, n);
+    points.fetch(sg); code.fetch(sg);
     int32_t acc = 0;
     for (size_t m = 0; m < n; ++m) acc += res->code[m] >= MOVBA_TRI_DLT && res->code[m] <= MOVBA_TRI_STEREO2;
     res->n_accepted = acc;

@@ -6,6 +6,7 @@
 // buffer and are copied out.  The hypothesis tables (hyp_nsol / hyp_E / hyp_loss) stay in device scratch and are copied
 // only for a caller that asks for them.  The refit's per-pair slots (TvDev::lo) exist only when a refit or `info` is asked
 // for: they go up zero-filled with the inputs and come back with one copy more before the synchronisation.
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <vector>
@@ -98,11 +99,12 @@ int two_view_front(movba_handle *h, const movba_two_view_desc *descs, movba_two_
     // Device arena: [0, h2d) the inputs (one H2D copy), then scratch.  Staging buffer: the same inputs, then the results that
     // do not go straight into the caller's pinned arrays.
     Carver c;
-    const size_t o_pairs = c.take<TvPair>(np), o_first = c.take<int32_t>(np + 1);
-    const size_t o_obs1 = c.take<double>(2 * M), o_obs2 = c.take<double>(2 * M), o_samp = c.take<int32_t>(5 * H);
+    In<TvPair> in_pairs;
+    In<int32_t> first, samp;
+    In<double> obs1, obs2, lo;
+    in_pairs.plan(np, c); first.plan(np + 1, c); obs1.plan(2 * M, c); obs2.plan(2 * M, c); samp.plan(5 * H, c);
     const bool want_lo = lo_iters > 0 || info;
-    const size_t lo_bytes = want_lo ? sizeof(double) * kTvLoDoubles * np : 0;
-    const size_t o_lo = c.take<double>(lo_bytes / sizeof(double));
+    lo.plan(want_lo ? kTvLoDoubles * np : 0, c);
     const size_t h2d = c.off;
     Carver dv = c;
     const size_t o_cand = dv.take<double>(90 * H), o_loss = dv.take<double>(10 * H), o_cnt = dv.take<int32_t>(10 * H);
@@ -116,66 +118,56 @@ int two_view_front(movba_handle *h, const movba_two_view_desc *descs, movba_two_
     for (int j = 0; j < n; ++j) results[j].status = MOVBA_ERR_HIP;      // (until the device work is through)
     int rc = begin_side_call(h, dev_total, total); if (rc) return rc;
 
-    char *sg = h->stage, *ar = h->pose_scratch.p;
-    struct View { unsigned long long *inl, *pts, *good, *code; };
-    std::vector<View> views(np);
+    char *sg = h->stage, *ar = h->pose_scratch.p, *sd = h->stage_dev;
+    struct PairOut { Out<uint8_t> inl, good, code; Out<double> pts; };     // each pair's share of the per-match results
+    std::vector<PairOut> outs(np);
     for (int k = 0; k < n; ++k) {
         const movba_two_view_desc &d = descs[k];
         movba_two_view_result &r = results[k];
         TvPair &p = pairs[k];
-        const size_t m = (size_t)p.n;
-        View &v = views[k];
-        v.inl = m ? host_block_view(r.inlier, m) : nullptr; v.pts = m ? host_block_view(r.points, sizeof(double) * 3 * m) : nullptr;
-        v.good = m ? host_block_view(r.good, m) : nullptr; v.code = m ? host_block_view(r.code, m) : nullptr;
-        p.inlier = v.inl ? reinterpret_cast<uint8_t *>(v.inl) : reinterpret_cast<uint8_t *>(h->stage_dev + o_inl) + p.m0;
-        p.points = v.pts ? reinterpret_cast<double *>(v.pts) : reinterpret_cast<double *>(h->stage_dev + o_pts) + 3 * (size_t)p.m0;
-        p.good = v.good ? reinterpret_cast<uint8_t *>(v.good) : reinterpret_cast<uint8_t *>(h->stage_dev + o_good) + p.m0;
-        p.code = v.code ? reinterpret_cast<uint8_t *>(v.code) : reinterpret_cast<uint8_t *>(h->stage_dev + o_code) + p.m0;
-        p.out = reinterpret_cast<double *>(h->stage_dev + o_out) + (size_t)kTvOutDoubles * k;
+        const size_t m = (size_t)p.n, m0 = (size_t)p.m0;
+        PairOut &v = outs[k];
+        v.inl.plan_within(r.inlier, m, o_inl, m0); v.pts.plan_within(r.points, 3 * m, o_pts, 3 * m0);
+        v.good.plan_within(r.good, m, o_good, m0); v.code.plan_within(r.code, m, o_code, m0);
+        v.inl.bind(sd); v.pts.bind(sd); v.good.bind(sd); v.code.bind(sd);
+        p.inlier = v.inl.dev; p.points = v.pts.dev; p.good = v.good.dev; p.code = v.code.dev;
+        p.out = at<double>(sd, o_out) + (size_t)kTvOutDoubles * k;
         if (m) {
-            std::memcpy(sg + o_obs1 + sizeof(double) * 2 * (size_t)p.m0, d.obs1, sizeof(double) * 2 * m);
-            std::memcpy(sg + o_obs2 + sizeof(double) * 2 * (size_t)p.m0, d.obs2, sizeof(double) * 2 * m);
-            (void)movba_two_view_samples(p.n, p.n_hyp, d.ransac_seed, reinterpret_cast<int32_t *>(sg + o_samp) + 5 * (size_t)p.h0);
+            std::copy_n(d.obs1, 2 * m, obs1.host(sg) + 2 * m0);
+            std::copy_n(d.obs2, 2 * m, obs2.host(sg) + 2 * m0);
+            (void)movba_two_view_samples(p.n, p.n_hyp, d.ransac_seed, samp.host(sg) + 5 * (size_t)p.h0);
         }
     }
-    std::memcpy(sg + o_pairs, pairs.data(), sizeof(TvPair) * np);
-    std::memcpy(sg + o_first, hyp_first.data(), sizeof(int32_t) * (np + 1));
-    if (want_lo) std::memset(sg + o_lo, 0, lo_bytes);
+    in_pairs.fill(sg, pairs.data()); first.fill(sg, hyp_first.data());
+    std::fill_n(lo.host(sg), lo.count, 0.0);
 
     TvDev t{};
     t.n_pairs = n; t.n_hyp_total = (int32_t)H;
-    t.pairs = reinterpret_cast<const TvPair *>(ar + o_pairs); t.hyp_first = reinterpret_cast<const int32_t *>(ar + o_first);
-    t.obs1 = reinterpret_cast<const double *>(ar + o_obs1); t.obs2 = reinterpret_cast<const double *>(ar + o_obs2);
-    t.samples = reinterpret_cast<const int32_t *>(ar + o_samp);
-    t.cand = reinterpret_cast<double *>(ar + o_cand); t.loss = reinterpret_cast<double *>(ar + o_loss);
-    t.cnt = reinterpret_cast<int32_t *>(ar + o_cnt); t.nsol = reinterpret_cast<int32_t *>(ar + o_nsol);
-    t.inl0 = reinterpret_cast<uint8_t *>(ar + o_inl0); t.cosv = reinterpret_cast<double *>(ar + o_cos);
-    t.rec = reinterpret_cast<double *>(ar + o_rec);
-    t.lo = want_lo ? reinterpret_cast<double *>(ar + o_lo) : nullptr;
+    t.pairs = in_pairs.dev(ar); t.hyp_first = first.dev(ar); t.obs1 = obs1.dev(ar); t.obs2 = obs2.dev(ar); t.samples = samp.dev(ar);
+    t.cand = at<double>(ar, o_cand); t.loss = at<double>(ar, o_loss); t.cnt = at<int32_t>(ar, o_cnt); t.nsol = at<int32_t>(ar, o_nsol);
+    t.inl0 = at<uint8_t>(ar, o_inl0); t.cosv = at<double>(ar, o_cos); t.rec = at<double>(ar, o_rec);
+    t.lo = want_lo ? at<double>(ar, lo.off) : nullptr;      // (an input the refit writes back: not const)
     t.lo_iters = lo_iters;
 
     HIP_TRY(hipMemcpyAsync(ar, sg, h2d, hipMemcpyHostToDevice, h->stream));
     HIP_TRY(launch_two_view(t, h->stream));
-    if (want_lo) HIP_TRY(hipMemcpyAsync(sg + o_lo, ar + o_lo, lo_bytes, hipMemcpyDeviceToHost, h->stream));
+    if (want_lo) HIP_TRY(hipMemcpyAsync(sg + lo.off, ar + lo.off, sizeof(double) * lo.count, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
 
     for (int k = 0; k < n; ++k) {
         movba_two_view_result &r = results[k];
         const TvPair &p = pairs[k];
         const size_t m = (size_t)p.n;
-        const View &v = views[k];
-        if (m && !v.inl) std::memcpy(r.inlier, sg + o_inl + p.m0, m);
-        if (m && !v.pts) std::memcpy(r.points, sg + o_pts + sizeof(double) * 3 * (size_t)p.m0, sizeof(double) * 3 * m);
-        if (m && !v.good) std::memcpy(r.good, sg + o_good + p.m0, m);
-        if (m && !v.code) std::memcpy(r.code, sg + o_code + p.m0, m);
-        const double *o = reinterpret_cast<const double *>(sg + o_out) + (size_t)kTvOutDoubles * k;
+        const PairOut &v = outs[k];
+        v.inl.fetch(sg); v.pts.fetch(sg); v.good.fetch(sg); v.code.fetch(sg);
+        const double *o = at<const double>(sg, o_out) + (size_t)kTvOutDoubles * k;
         for (int e = 0; e < 7; ++e) r.pose[e] = o[e];
         for (int e = 0; e < 9; ++e) r.E[e] = o[7 + e];
         r.parallax_deg = o[16]; r.outcome = (int32_t)o[17]; r.n_inliers = (int32_t)o[18]; r.n_pass = (int32_t)o[19];
         r.n_good = (int32_t)o[20]; r.samples_used = (int32_t)o[21];
         if (info) {
             // (a slot no kernel wrote - no winner, fewer than 5 matches - is still the zeros that went up)
-            const double *l = reinterpret_cast<const double *>(sg + o_lo) + (size_t)kTvLoDoubles * k;
+            const double *l = lo.host(sg) + (size_t)kTvLoDoubles * k;
             movba_two_view_lo_info &fo = info[k];
             fo.loss0 = l[18]; fo.loss = l[19];
             for (int e = 0; e < 9; ++e) fo.E0[e] = l[9 + e];

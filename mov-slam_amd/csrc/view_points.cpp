@@ -65,11 +65,6 @@ bool vp_desc_ok(const movba_view_desc &d, const movba_view_result &r)
     return true;
 }
 
-template <typename T> void put(char *stage, size_t off, const T *src, size_t count)
-{
-    std::memcpy(stage + off, src, sizeof(T) * count);
-}
-
 }  // namespace
 
 extern "C" int movba_view_points(movba_handle *h, const movba_view_desc *desc, movba_view_result *res)
@@ -116,12 +111,14 @@ extern "C" int movba_view_points(movba_handle *h, const movba_view_desc *desc, m
     const size_t nc = chunks.size();
 
     // Layout.  [0, h2d): the inputs, one H2D copy into the handle's pose scratch.  Behind them on the device: the select's keys
-    // and the codes k_vp_views counts; behind them in the staging buffer: the results that do not go straight into the caller's
-    // pinned arrays.
+    // and the codes k_vp_views counts; behind them in the staging buffer: the results (Out: those that are staged).
     Carver c;
-    const size_t o_views = c.take<VpView>(nv), o_chunks = c.take<VpChunk>(nc), o_item = c.take<int32_t>(n);
-    const size_t o_pts = c.take<double>(3 * np);
-    const size_t o_nrm = table ? c.take<double>(3 * np) : 0, o_max = table ? c.take<double>(np) : 0, o_min = table ? c.take<double>(np) : 0;
+    In<VpView> in_views;
+    In<VpChunk> in_chunks;
+    In<int32_t> item;
+    In<double> pts, nrm, dmax, dmin;
+    in_views.plan(nv, c); in_chunks.plan(nc, c); item.plan(n, c); pts.plan(3 * np, c);
+    nrm.plan(table ? 3 * np : 0, c); dmax.plan(table ? np : 0, c); dmin.plan(table ? np : 0, c);
     const size_t h2d = c.off;
     Carver dv = c;
     const size_t o_keys = dv.take<uint64_t>(n_keys), o_cdev = dv.take<uint8_t>(n);
@@ -136,20 +133,15 @@ extern "C" int movba_view_points(movba_handle *h, const movba_view_desc *desc, m
     res->status = MOVBA_ERR_HIP;            // (until the device work is through)
     int rc = begin_side_call(h, dv.off, total); if (rc) return rc;
 
-    char *sg = h->stage, *ar = h->pose_scratch.p;
-    put(sg, o_views, views.data(), nv); put(sg, o_chunks, chunks.data(), nc); put(sg, o_item, d.item_point, n);
-    put(sg, o_pts, d.points, 3 * np);
-    if (table) { put(sg, o_nrm, d.normals, 3 * np); put(sg, o_max, d.max_distance, np); put(sg, o_min, d.min_distance, np); }
+    char *sg = h->stage, *ar = h->pose_scratch.p, *sd = h->stage_dev;
+    in_views.fill(sg, views.data()); in_chunks.fill(sg, chunks.data()); item.fill(sg, d.item_point);
+    pts.fill(sg, d.points); nrm.fill(sg, d.normals); dmax.fill(sg, d.max_distance); dmin.fill(sg, d.min_distance);
 
-    auto dbl = [&](size_t off) { return reinterpret_cast<const double *>(ar + off); };
     VpDev t{};
     t.n_views = d.n_views; t.n_chunks = (int32_t)nc;
-    t.views = reinterpret_cast<const VpView *>(ar + o_views); t.chunks = reinterpret_cast<const VpChunk *>(ar + o_chunks);
-    t.item_point = reinterpret_cast<const int32_t *>(ar + o_item);
-    t.points = dbl(o_pts);
-    if (table) { t.normals = dbl(o_nrm); t.max_dist = dbl(o_max); t.min_dist = dbl(o_min); }
-    t.keys = reinterpret_cast<uint64_t *>(ar + o_keys); t.code_dev = reinterpret_cast<uint8_t *>(ar + o_cdev);
-    char *sd = h->stage_dev;
+    t.views = in_views.dev(ar); t.chunks = in_chunks.dev(ar); t.item_point = item.dev(ar);
+    t.points = pts.dev(ar); t.normals = nrm.dev(ar); t.max_dist = dmax.dev(ar); t.min_dist = dmin.dev(ar);
+    t.keys = at<uint64_t>(ar, o_keys); t.code_dev = at<uint8_t>(ar, o_cdev);
     code.bind(sd); z.bind(sd); uv.bind(sd); dist.bind(sd); vcos.bind(sd); level.bind(sd); ur.bind(sd); depth.bind(sd);
     nacc.bind(sd); median.bind(sd);
     t.code = code.dev; t.z = z.dev; t.uv = uv.dev; t.dist = dist.dev; t.view_cos = vcos.dev; t.level = level.dev; t.ur = ur.dev;

@@ -406,9 +406,11 @@ TWO_VIEW_DEFAULTS = dict(threshold=1.0, confidence=0.999, sigma=1.0, min_paralla
                          ransac_iters=256, ransac_seed=1)
 
 
-def two_view_desc(pair, alloc=np.zeros, diagnostics=False):
+def two_view_desc(pair, alloc=np.zeros, diagnostics=False, alloc_by=None):
     """One frame pair - dict(obs1, obs2 (M, 2), cam (fx, fy, cx, cy), optional TWO_VIEW_DEFAULTS keys) ->
-    (movba_two_view_desc, movba_two_view_result with its output arrays, the arrays both point into)."""
+    (movba_two_view_desc, movba_two_view_result with its output arrays, the arrays both point into).  alloc_by: allocators of
+    single result arrays by name, where they differ from alloc."""
+    mk = lambda key, shape, dtype: (alloc_by or {}).get(key, alloc)(shape, dtype)
     keep = dict(obs1=np.ascontiguousarray(pair["obs1"], np.float64).reshape(-1, 2),
                 obs2=np.ascontiguousarray(pair["obs2"], np.float64).reshape(-1, 2))
     m = len(keep["obs1"])
@@ -417,7 +419,8 @@ def two_view_desc(pair, alloc=np.zeros, diagnostics=False):
     d.fx, d.fy, d.cx, d.cy = pair["cam"]
     for key, val in TWO_VIEW_DEFAULTS.items():
         setattr(d, key, pair.get(key, val))
-    keep.update(inlier=alloc((m,), np.uint8), points=alloc((m, 3), np.float64), good=alloc((m,), np.uint8), code=alloc((m,), np.uint8))
+    keep.update(inlier=mk("inlier", (m,), np.uint8), points=mk("points", (m, 3), np.float64), good=mk("good", (m,), np.uint8),
+                code=mk("code", (m,), np.uint8))
     r = TwoViewResult()
     r.inlier = _p(keep["inlier"], _u); r.points = _p(keep["points"], _d); r.good = _p(keep["good"], _u); r.code = _p(keep["code"], _u)
     if diagnostics:
@@ -430,10 +433,11 @@ def two_view_desc(pair, alloc=np.zeros, diagnostics=False):
 INIT_MAP_DEFAULTS = dict(max_iters=20, max_trials=0, min_tracked=50, huber_delta=float(np.sqrt(np.float32(5.0))))
 
 
-def init_map_desc(pair, alloc=np.zeros, chi2=True):
+def init_map_desc(pair, alloc=np.zeros, chi2=True, alloc_by=None):
     """One frame pair - dict(obs1, obs2 (M, 2), points (M, 3), pose2 (7,), cam (fx, fy, cx, cy), optional use (M,),
     inv_sigma2_1, inv_sigma2_2 (M,) and the keys of INIT_MAP_DEFAULTS) -> (movba_init_map_desc, movba_init_map_result with its
-    output arrays, the arrays both point into)."""
+    output arrays, the arrays both point into).  alloc_by: as two_view_desc."""
+    mk = lambda key, shape, dtype: (alloc_by or {}).get(key, alloc)(shape, dtype)
     keep = dict(obs1=np.ascontiguousarray(pair["obs1"], np.float64).reshape(-1, 2),
                 obs2=np.ascontiguousarray(pair["obs2"], np.float64).reshape(-1, 2),
                 points_in=np.ascontiguousarray(pair["points"], np.float64).reshape(-1, 3))
@@ -451,11 +455,11 @@ def init_map_desc(pair, alloc=np.zeros, chi2=True):
     d.fx, d.fy, d.cx, d.cy = pair["cam"]
     for key, val in INIT_MAP_DEFAULTS.items():
         setattr(d, key, pair.get(key, val))
-    keep["points"] = alloc((m, 3), np.float64)
+    keep["points"] = mk("points", (m, 3), np.float64)
     r = InitMapResult()
     r.points = _p(keep["points"], _d)
     if chi2:
-        keep["chi2"] = alloc((m, 2), np.float64)
+        keep["chi2"] = mk("chi2", (m, 2), np.float64)
         r.chi2 = _p(keep["chi2"], _d)
     return d, r, keep
 
@@ -799,19 +803,28 @@ class Solver:
             raise MovbaError(f"movba_triangulate: {status_string(rc)}")
         return dict(points=points, code=code, n_accepted=r.n_accepted, status=rc)
 
+    def _pair_alloc(self, pinned, k):
+        """(alloc, alloc_by) of pair k's result arrays for two_view_desc / init_map_desc: pinned is one flag for every array
+        of every pair, or a sequence with one set of array names per pair."""
+        if np.isscalar(pinned):
+            return (self._pinned if pinned else np.zeros), None
+        return np.zeros, {name: self._pinned for name in pinned[k]}
+
     def two_view(self, pairs, pinned=False, diagnostics=False, lo_iters=None) -> list:
         """movba_two_view (monocular map initialisation, TwoViewReconstruction::Reconstruct) on a list of frame pairs:
         dicts with obs1, obs2 (M, 2) pixels, cam (fx, fy, cx, cy) and optionally the keys of TWO_VIEW_DEFAULTS.  One dict per
         pair back: status (0, or 3 = MOVBA_EMPTY under 5 matches), outcome (TV_*), pose (T21), E (3, 3), parallax_deg,
         n_inliers, n_pass, n_good, samples_used, inlier, points, good, code (TV_CHK_*) per match and, with diagnostics,
         hyp_nsol, hyp_E, hyp_loss.  pinned: per-match arrays in movba_host_alloc memory (written by the kernels; they live
-        until close()).  lo_iters: None calls movba_two_view; an integer calls movba_two_view_lo (local optimisation of the
-        winner with that many steps at most) and adds lo_kept, lo_steps, loss0, loss, n_inliers0 and E0 (3, 3) to every dict."""
+        until close()) - True / False for all of them, or a sequence with one set of array names per pair.  lo_iters: None
+        calls movba_two_view; an integer calls movba_two_view_lo (local optimisation of the winner with that many steps at
+        most) and adds lo_kept, lo_steps, loss0, loss, n_inliers0 and E0 (3, 3) to every dict."""
         n = len(pairs)
         descs = (TwoViewDesc * max(n, 1))(); res = (TwoViewResult * max(n, 1))()
         keeps = []
         for k, pair in enumerate(pairs):
-            d, r, keep = two_view_desc(pair, self._pinned if pinned else np.zeros, diagnostics)
+            alloc, by = self._pair_alloc(pinned, k)
+            d, r, keep = two_view_desc(pair, alloc, diagnostics, alloc_by=by)
             descs[k] = d; res[k] = r
             keeps.append(keep)
         if lo_iters is None:
@@ -841,13 +854,15 @@ class Solver:
         pose, points and good go in as pose2, points and use.  One dict per pair back: status (0, or 3 = MOVBA_EMPTY without
         a used match), outcome (IM_*), pose (T21), points (M, 3), chi2 (M, 2), median_depth, n_used, iters_done, n_solves,
         last_rejected, n_chol_fail, lam, cost0, cost and, with trace, trace = dict(lam, f0, f1, rho, accept).  pinned:
-        per-match arrays in movba_host_alloc memory (written by the kernel; they live until close())."""
+        per-match arrays in movba_host_alloc memory (written by the kernel; they live until close()) - as two_view.  A pair
+        with chi2=False leaves chi2 out (None comes back)."""
         n = len(pairs)
         descs = (InitMapDesc * max(n, 1))(); res = (InitMapResult * max(n, 1))()
         tr = (InitMapTrace * max(n, 1))() if trace else None
         keeps = []
         for k, pair in enumerate(pairs):
-            d, r, keep = init_map_desc(pair, self._pinned if pinned else np.zeros)
+            alloc, by = self._pair_alloc(pinned, k)
+            d, r, keep = init_map_desc(pair, alloc, pair.get("chi2", True), alloc_by=by)
             descs[k] = d; res[k] = r
             keeps.append(keep)
         rc = self._L.movba_init_map(self._h, descs, res, n, tr)
@@ -856,7 +871,7 @@ class Solver:
         out = []
         for k in range(n):
             r, keep = res[k], keeps[k]
-            o = dict(status=r.status, outcome=r.outcome, pose=np.array(r.pose[:]), points=keep["points"], chi2=keep["chi2"],
+            o = dict(status=r.status, outcome=r.outcome, pose=np.array(r.pose[:]), points=keep["points"], chi2=keep.get("chi2"),
                      median_depth=r.median_depth, n_used=r.n_used, iters_done=r.iters_done, n_solves=r.n_solves,
                      last_rejected=r.last_rejected, n_chol_fail=r.n_chol_fail, lam=r.lambda_, cost0=r.cost0, cost=r.cost)
             if trace:

@@ -108,6 +108,21 @@ def test_a_batch_equals_its_solo_calls_permutes_repeats_and_ignores_where_result
     assert all(same_bits(x, y) for x, y in zip(solver.init_map(pairs, pinned=True, trace=True), a))
 
 
+def test_placement_mixed_per_pair_and_per_array_gives_the_same_bits(solver):
+    """pair 0: points pinned, chi2 ordinary; pair 1: chi2 pinned, points ordinary; pair 2: a mask that leaves no used match;
+    pair 3: chi2 left out - every result field and array as with everything in ordinary memory"""
+    cases = M.PAIRS()
+    pairs = [call_args(cases[5]), call_args(cases[6]), dict(call_args(cases[3]), use=np.zeros(12, np.uint8)),
+             dict(call_args(cases[10]), chi2=False)]
+    want = solver.init_map(pairs, trace=True)
+    got = solver.init_map(pairs, pinned=[{"points"}, {"chi2"}, set(), set()], trace=True)
+    assert [r["status"] for r in want] == [0, 0, capi.EMPTY, 0] and want[3]["chi2"] is None and got[3]["chi2"] is None
+    assert want[3]["points"][M.used(pairs[3])].any() and not want[2]["points"].any()
+    none = np.zeros((0, 2))
+    for k, (a, b) in enumerate(zip(want, got)):
+        assert same_bits(dict(a, chi2=none) if k == 3 else a, dict(b, chi2=none) if k == 3 else b), k
+
+
 def test_the_mask_layout_gives_the_bits_of_the_compacted_layout(solver):
     compact = [call_args(M.make_pair(n, sc, seed=500 + n, mismatch=0.03)) for n, sc in ((1, "general"), (65, "planar"), (257, "forward"), (300, "general"))]
     spread = [M.spread_out(p, 3) for p in compact] + [M.spread_out(p, 4, fill=1e300) for p in compact]

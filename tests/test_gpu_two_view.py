@@ -84,6 +84,19 @@ def test_pinned_and_ordinary_result_memory_give_the_same_bits(solver):
             assert np.array_equal(x[k].view(np.uint8), y[k].view(np.uint8))
 
 
+def test_placement_mixed_per_pair_and_per_array_gives_the_same_bits(solver):
+    """pair 0: points and code pinned, inlier and good ordinary; pair 1 (12 matches) the other way round; pair 2 (4 matches:
+    not solved) all ordinary - every result field and array as with everything in ordinary memory"""
+    pairs = [pair_of(args, iters, seed) for _, args, iters, seed in T.SCENES[:3]]
+    for p, m in ((pairs[1], 12), (pairs[2], 4)):
+        p["obs1"], p["obs2"] = p["obs1"][:m], p["obs2"][:m]
+    want = solver.two_view(pairs)
+    got = solver.two_view(pairs, pinned=[{"points", "code"}, {"inlier", "good"}, set()])
+    assert [g["status"] for g in want] == [0, 0, 3] and [len(g["code"]) for g in want] == [500, 12, 4]
+    for k, (a, b) in enumerate(zip(want, got)):
+        assert same_bits(a, b), f"pair {k} differs between mixed and ordinary result memory"
+
+
 def test_an_uploaded_window_solves_to_the_same_bits_after_a_call(built_lib):
     w = synth.cfg("small")
     s = built_lib.Solver()
