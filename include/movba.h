@@ -831,6 +831,82 @@ int  movba_point_normals(movba_handle *h, const movba_normals_desc *desc, movba_
 int  movba_lba_point_normals(movba_handle *h, const int32_t *ref_pose, const int32_t *ref_level, const double *scale_factors,
                              int32_t n_levels, const uint8_t *outlier, double *normals, double *max_distance, double *min_distance);
 
+/* The covisibility count for many keyframes or frames per call: "for each map point of this keyframe, for each keyframe that
+ * observes it, counter[keyframe]++", then the threshold, the maximum and the ordering - the numeric body of
+ * KeyFrame::UpdateConnections (KeyFrame.cc:367-459, run after ProcessNewKeyFrame, SearchInNeighbors and both initialisations),
+ * of the voting loop of Tracking::UpdateLocalKeyFrames with its choice of mpReferenceKF (Tracking.cc:1200-1280) and of the count
+ * that gives a local window its fixed keyframes (Optimizer.cc:506-522).  Its output decides what the other calls are fed: the
+ * neighbours handed to movba_triangulate (GetBestCovisibilityKeyFrames), the views handed to movba_view_points, the window handed
+ * to movba_lba_upload.  A query is one keyframe or frame, given as the list of its map points; the observation lists are the
+ * prefix array movba_point_normals takes.  Everything is integer: the result is exact. */
+#define MOVBA_MAX_COVIS_VIEWS   8192
+#define MOVBA_MAX_COVIS_QUERIES 4096
+
+typedef struct {
+    int32_t n_views, n_points, n_queries;
+    int32_t min_weight;             /* th = 15 (KeyFrame.cc:408); >= 1                                                      */
+    int32_t max_out;                /* entries of the ordered list handed out per query, >= 0                               */
+    int32_t pad;
+    const int32_t *obs_ptr;         /* n_points + 1, as movba_normals_desc::obs_ptr; n_obs = obs_ptr[n_points]              */
+    const int32_t *obs_view;        /* n_obs: the observers of each point (MapPoint::GetObservations, :390)                 */
+    const uint8_t *eligible;        /* n_views or NULL (all): 0 = the view is never counted (isBad() || GetMap() != mpMap,
+                                       KeyFrame.cc:394; isBad, Tracking.cc:1269)                                            */
+    const int32_t *query_ptr;       /* n_queries + 1, ascending, [0] = 0; n_items = query_ptr[n_queries]                    */
+    const int32_t *query_point;     /* n_items: the non-null, non-bad mvpMapPoints of the query, slot order (:380-388)      */
+    const int32_t *query_self;      /* n_queries or NULL (all -1): the query's own view (mnId == mnId is skipped,
+                                       KeyFrame.cc:394); -1: a Frame, nothing is skipped (Tracking.cc:1217)                 */
+} movba_covis_desc;     /* 72 bytes */
+
+typedef struct {
+    int32_t *n_counted;             /* n_queries: views with a count > 0 (KFcounter.size())                                 */
+    int32_t *n_connected;           /* n_queries: see below                                                                 */
+    int32_t *best_view;             /* n_queries: pKFmax (:421, Tracking.cc:1275), -1 when n_counted == 0                   */
+    int32_t *best_weight;           /* n_queries: nmax, 0 when n_counted == 0                                               */
+    int32_t *out_view;              /* n_queries x max_out, or NULL when max_out == 0                                       */
+    int32_t *out_weight;            /* n_queries x max_out, or NULL when max_out == 0                                       */
+    int32_t  status, pad;
+} movba_covis_result;   /* 56 bytes */
+
+/* Restated as written, query by query:
+ *   count      weight[q][v] = sum over the items i of query q of the number of times v occurs in the list of query_point[i]
+ *              (:380-398), for the views v with eligible[v] != 0 and v != query_self[q]; the others are never counted.  A point
+ *              that occupies two slots counts twice, as in the loop over mvpMapPoints.  The lists are not checked for duplicate
+ *              observers: one that names a view twice counts it twice.
+ *   order      the reference sorts vPairs ascending by (weight, pointer) and pushes to the front (:436-443).  Here the view
+ *              index stands where the pointer stood, and that is the only freedom taken: the ordered list of a query is all its
+ *              counted views by weight descending, ties by view index descending.  out_view / out_weight of query q hold its
+ *              first min(n_counted, max_out) entries; behind those out_view holds -1 and out_weight 0.  With max_out <
+ *              n_counted the hand-out is a prefix of the full order, and n_counted shows the truncation.
+ *   best       `>` in map order (:418, Tracking.cc:1272) keeps the first maximum: best_view is the LOWEST view index among
+ *              the views of maximal weight.  On a tie at the top best_view != out_view[0] - as written in the reference, where
+ *              mpParent is the front of the list (:454) and pKFmax is not.
+ *   connected  n_connected = the number of counted views with weight >= min_weight, not capped by max_out: they are the leading
+ *              entries of the order (mvpOrderedConnectedKeyFrames, mvOrderedWeights).  If no view reaches min_weight and
+ *              n_counted > 0, n_connected = 1 and the one connection is (best_view, best_weight) (:430-434), not necessarily
+ *              out_view[0].  n_counted == 0: n_connected = 0 (the reference returns at :401).
+ * What stays with the caller: AddConnection on the other keyframes, the parent / child bookkeeping and
+ * mConnectedKeyFrameWeights as a map (the full counter is the ordered list with max_out = n_views); the neighbour / child /
+ * parent expansion of UpdateLocalKeyFrames (Tracking.cc:1282-1332) with its breaks; the mnBALocalForKF marks of
+ * LocalBundleAdjustment.
+ * A query's result depends on its own items, its query_self entry, the lists those items name and `eligible` - not on the other
+ * queries, their order, or how the queries are split over calls - and two calls give the same bits: the sums are integer (LDS
+ * atomics, which commute), floating point does not occur.
+ * Returns MOVBA_ERR_ARG for a NULL handle, descriptor or result; a negative count (n_views, n_points, n_queries, max_out);
+ * n_views > MOVBA_MAX_COVIS_VIEWS; n_queries > MOVBA_MAX_COVIS_QUERIES; n_obs or n_items above 2^28; n_queries x max_out above
+ * 2^28; min_weight < 1; obs_ptr or query_ptr not ascending or not starting at 0; an observer index outside 0 .. n_views - 1; a
+ * point index outside 0 .. n_points - 1; a query_self outside -1 .. n_views - 1; a query whose items' lists hold more than
+ * 2^31 - 1 entries together (its weights would not fit); a NULL array that the counts make necessary (the four per-query result
+ * arrays, query_ptr, and out_view / out_weight when max_out > 0, when n_queries > 0; obs_ptr when n_points > 0; obs_view when
+ * n_obs > 0; query_point when n_items > 0).  MOVBA_ERR_HIP as elsewhere.  Every argument is checked before anything is queued,
+ * and on a non-zero status nothing is written except `status`.  n_queries == 0 (with counts that are otherwise in range):
+ * MOVBA_OK and nothing else written, the arrays are not looked at.
+ * One packed copy to the device, one launch - k_covis, one workgroup per query: the query's counters and sort keys live in the
+ * workgroup's LDS, which is what bounds n_views; a caller whose map is larger renumbers the views its queries can reach - and
+ * one synchronisation; result arrays that lie in movba_host_alloc memory are written by the kernel itself.  May share a handle
+ * with an uploaded or solved window, waiting for the window's arrays before it reuses the staging buffer: the window, its
+ * results, its marginals and later runs stay as they were. */
+int  movba_covisibility(movba_handle *h, const movba_covis_desc *desc, movba_covis_result *res);
+
 #ifdef __cplusplus
 }
 #endif

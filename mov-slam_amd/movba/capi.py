@@ -157,6 +157,20 @@ class NormalsResult(C.Structure):
     _fields_ = [("normals", _d), ("max_distance", _d), ("min_distance", _d), ("status", C.c_int32), ("pad", C.c_int32)]
 
 
+class CovisDesc(C.Structure):
+    _fields_ = [("n_views", C.c_int32), ("n_points", C.c_int32), ("n_queries", C.c_int32), ("min_weight", C.c_int32),
+                ("max_out", C.c_int32), ("pad", C.c_int32), ("obs_ptr", _i), ("obs_view", _i), ("eligible", _u),
+                ("query_ptr", _i), ("query_point", _i), ("query_self", _i)]
+
+
+class CovisResult(C.Structure):
+    _fields_ = [("n_counted", _i), ("n_connected", _i), ("best_view", _i), ("best_weight", _i), ("out_view", _i),
+                ("out_weight", _i), ("status", C.c_int32), ("pad", C.c_int32)]
+
+
+MAX_COVIS_VIEWS = 8192
+MAX_COVIS_QUERIES = 4096
+COVIS_ARRAYS = ("n_counted", "n_connected", "best_view", "best_weight", "out_view", "out_weight")
 MAX_INIT_MAP_ITERS = 100
 # movba_init_map_result::outcome (MOVBA_IM_*)
 IM_OK, IM_NEG_DEPTH, IM_FEW_TRACKED = 0, 1, 2
@@ -192,7 +206,7 @@ EXPORTS = ["movba_version", "movba_status_string", "movba_create", "movba_destro
            "movba_structure_probe", "movba_pose_opt", "movba_set_profile_mask", "movba_lba_run_batch", "movba_pose_ransac_samples",
            "movba_host_alloc", "movba_host_free", "movba_dense_plan_probe", "movba_pose_opt_batch", "movba_lba_marginals", "movba_triangulate",
            "movba_two_view", "movba_two_view_samples", "movba_two_view_lo", "movba_init_map", "movba_view_points",
-           "movba_point_normals", "movba_lba_point_normals"]
+           "movba_point_normals", "movba_lba_point_normals", "movba_covisibility"]
 
 _libs = {False: None, True: None}
 
@@ -256,6 +270,7 @@ def lib(hooks: bool = False):
         L.movba_view_points.argtypes = [C.c_void_p, C.POINTER(ViewDesc), C.POINTER(ViewResult)]
         L.movba_point_normals.argtypes = [C.c_void_p, C.POINTER(NormalsDesc), C.POINTER(NormalsResult)]
         L.movba_lba_point_normals.argtypes = [C.c_void_p, _i, _i, _d, C.c_int32, _u, _d, _d, _d]
+        L.movba_covisibility.argtypes = [C.c_void_p, C.POINTER(CovisDesc), C.POINTER(CovisResult)]
         L.movba_host_alloc.argtypes = [C.c_size_t]
         L.movba_host_alloc.restype = C.c_void_p
         L.movba_dense_plan_probe.argtypes = [C.c_int32, C.c_int32, C.c_int32, _i, _i, C.c_int32, _i, C.c_int32]
@@ -540,6 +555,46 @@ def normals_result(n_points, alloc=np.zeros):
     keep = dict(normals=alloc((n_points, 3), np.float64), max_distance=alloc((n_points,), np.float64), min_distance=alloc((n_points,), np.float64))
     r = NormalsResult()
     r.normals = _p(keep["normals"], _d); r.max_distance = _p(keep["max_distance"], _d); r.min_distance = _p(keep["min_distance"], _d)
+    return r, keep
+
+
+def covis_desc(n_views, lists, queries, query_self=None, eligible=None, min_weight=15, max_out=None):
+    """n_views, lists: one sequence of view indices per map point (its observers), queries: one sequence of point indices per
+    keyframe or frame (its map points, slot order), query_self (Q,) the queries' own views (-1: a frame) or None, eligible (V,)
+    or None, max_out: entries of the ordered list per query (None: n_views, the full counter) -> (movba_covis_desc, the arrays it
+    points into)."""
+    lists = [np.asarray(l, np.int32).reshape(-1) for l in lists]
+    queries = [np.asarray(q, np.int32).reshape(-1) for q in queries]
+    keep = dict(obs_ptr=np.concatenate([[0], np.cumsum([len(l) for l in lists])]).astype(np.int32),
+                obs_view=np.ascontiguousarray(np.concatenate(lists) if lists else np.zeros(0), np.int32),
+                query_ptr=np.concatenate([[0], np.cumsum([len(q) for q in queries])]).astype(np.int32),
+                query_point=np.ascontiguousarray(np.concatenate(queries) if queries else np.zeros(0), np.int32))
+    d = CovisDesc()
+    d.n_views, d.n_points, d.n_queries = int(n_views), len(lists), len(queries)
+    d.min_weight, d.max_out = int(min_weight), int(n_views if max_out is None else max_out)
+    for key in ("obs_ptr", "obs_view", "query_ptr", "query_point"):
+        setattr(d, key, _p(keep[key], _i))
+    if query_self is not None:
+        keep["query_self"] = np.ascontiguousarray(query_self, np.int32).reshape(-1)
+        if len(keep["query_self"]) != len(queries):
+            raise ValueError("covis_desc: query_self has one entry per query")
+        d.query_self = _p(keep["query_self"], _i)
+    if eligible is not None:
+        keep["eligible"] = np.ascontiguousarray(eligible, np.uint8).reshape(-1)
+        if len(keep["eligible"]) != d.n_views:
+            raise ValueError("covis_desc: eligible has one entry per view")
+        d.eligible = _p(keep["eligible"], _u)
+    return d, keep
+
+
+def covis_result(n_queries, max_out, alloc=np.zeros):
+    """-> (movba_covis_result with its output arrays, the arrays it points into); out_view / out_weight are (Q, max_out)"""
+    keep = {key: alloc((n_queries,), np.int32) for key in COVIS_ARRAYS[:4]}
+    keep["out_view"], keep["out_weight"] = alloc((n_queries, max_out), np.int32), alloc((n_queries, max_out), np.int32)
+    r = CovisResult()
+    for key in COVIS_ARRAYS:
+        if keep[key].size or key in COVIS_ARRAYS[:4]:
+            setattr(r, key, _p(keep[key], _i))
     return r, keep
 
 
@@ -910,6 +965,19 @@ class Solver:
         if rc < 0:
             raise MovbaError(f"movba_point_normals: {status_string(rc)}")
         out.update(status=rc)
+        return out
+
+    def covisibility(self, n_views, lists, queries, query_self=None, eligible=None, min_weight=15, max_out=None, pinned=False) -> dict:
+        """movba_covisibility (the count, threshold, maximum and ordering of KeyFrame::UpdateConnections and of the voting loop
+        of Tracking::UpdateLocalKeyFrames): arguments as covis_desc -> dict(status, n_counted, n_connected, best_view,
+        best_weight (Q,), out_view, out_weight (Q, max_out)): per query its counted views by weight descending, ties by view
+        index descending, padded with -1 / 0.  pinned: result arrays in movba_host_alloc memory, written by the kernel itself."""
+        d, keep = covis_desc(n_views, lists, queries, query_self, eligible, min_weight, max_out)
+        r, out = covis_result(d.n_queries, d.max_out, self._pinned if pinned else np.zeros)
+        rc = self._L.movba_covisibility(self._h, C.byref(d), C.byref(r))
+        if rc < 0:
+            raise MovbaError(f"movba_covisibility: {status_string(rc)}")
+        out["status"] = rc
         return out
 
     def lba_point_normals(self, ref_pose, ref_level, scale_factors, outlier=None, pinned=False) -> dict:
