@@ -45,7 +45,12 @@ static int run_lba(const char *in, const char *out, bool global)
     // every keyframe then has a GeometricCamera of its own (e->pCamera = pKFi->mpCamera, Optimizer.cc:664)
     std::vector<double> cam_kf, bf_kf;
     int32_t magic = 0;
-    if (fread(&magic, sizeof(int32_t), 1, f) == 1 && magic == 0x43414d31) { cam_kf = rd<double>(f, 4 * (size_t)NP); bf_kf = rd<double>(f, NP); }
+    bool more = fread(&magic, sizeof(int32_t), 1, f) == 1;
+    if (more && magic == 0x43414d31) { cam_kf = rd<double>(f, 4 * (size_t)NP); bf_kf = rd<double>(f, NP); more = fread(&magic, sizeof(int32_t), 1, f) == 1; }
+    // optional octave trailer (behind the stereo trailer and, when there is one, the camera trailer): the word 0x4f435431, then the
+    // pyramid level of every edge's keypoint - the edge's information is mvInvLevelSigma2[octave] (Optimizer.cc:657-658, 685-687)
+    std::vector<int32_t> octave;
+    if (more && magic == 0x4f435431) octave = rd<int32_t>(f, E);
     fclose(f);
 
     // $MOVBA_ADAPTER_REPS: the call repeated on a freshly built copy of the map; the LAST repetition is written out (its
@@ -75,7 +80,7 @@ static int run_lba(const char *in, const char *out, bool global)
     }
     for (int e = 0; e < E; ++e) {
         KeyFrame &k = kfs[ep[e]];
-        cv::KeyPoint kp; kp.pt.x = (float)obs[2 * e]; kp.pt.y = (float)obs[2 * e + 1]; kp.octave = 0;
+        cv::KeyPoint kp; kp.pt.x = (float)obs[2 * e]; kp.pt.y = (float)obs[2 * e + 1]; kp.octave = octave.empty() ? 0 : octave[e];
         const int idx = (int)k.mvKeysUn.size();
         fill(k.mvKeysUn).push_back(kp); fill(k.mvuRight).push_back(obs_right.empty() ? -1.f : (float)obs_right[e]); k.mvpMapPoints.push_back(&mps[el[e]]);
         mps[el[e]].AddObservation(&k, idx);               // (nObs as MapPoint.cc:139-169 counts it: a stereo observation twice)

@@ -47,7 +47,15 @@ public:
     const std::vector<cv::KeyPoint> mvKeysUn;
     const std::vector<float> mvuRight;
     const float mbf = 0.f;
-    const std::vector<float> mvInvLevelSigma2 = std::vector<float>(8, 1.0f);
+    // ORBextractor's table for 8 levels of scale 1.2, in float as it builds it: s[i] = s[i-1] * 1.2f, inv[i] = 1.0f / (s[i] * s[i])
+    // (1, 0.69444442, 0.48225307, 0.33489791, 0.23256798, 0.16150554, 0.11215661, 0.07788653)
+    static std::vector<float> InvLevelSigma2Table() {
+        std::vector<float> inv(8);
+        float s = 1.0f;
+        for (int i = 0; i < 8; ++i) { inv[i] = 1.0f / (s * s); s = s * 1.2f; }
+        return inv;
+    }
+    const std::vector<float> mvInvLevelSigma2 = InvLevelSigma2Table();
     GeometricCamera *mpCamera = nullptr, *mpCamera2 = nullptr;
     std::mutex mMutexPose, mMutexConnections, mMutexFeatures, mMutexMap;
     // test plumbing

@@ -375,6 +375,39 @@ def mixed_cameras(w: Window, seed: int, models=((320.0, 320.0, 320.0, 240.0), (4
 
 
 # ---------------------------------------------------------------------------------------------
+# Pyramid levels.  Every edge of the reference's local BA carries inv_sigma2 = mvInvLevelSigma2[octave] of its keypoint
+# (src/Optimizer.cc:657-658, 685-687, 724-725); the generators above give every edge the weight 1.
+# ---------------------------------------------------------------------------------------------
+def level_scale_factors(n_levels: int = 8, scale: float = 1.2, dtype=np.float32) -> np.ndarray:
+    """mvScaleFactors as the reference's extractor builds them: s[0] = 1, s[i] = s[i-1] * scale, every product rounded to
+    `dtype` (the extractor works in float; float64 gives the table in double)."""
+    s = np.ones(n_levels, dtype=dtype)
+    for i in range(1, n_levels):
+        s[i] = s[i - 1] * dtype(scale)
+    return s
+
+
+def level_inv_sigma2(n_levels: int = 8, scale: float = 1.2) -> np.ndarray:
+    """mvInvLevelSigma2 widened to double: inv[i] = 1.0f / (s[i] * s[i]) in float, then the cast the edge's
+    `const float &invSigma2` goes through (src/Optimizer.cc:657)."""
+    s = level_scale_factors(n_levels, scale, np.float32)
+    return (np.float32(1.0) / (s * s)).astype(np.float64)
+
+
+def with_levels(w: Window, seed: int, n_levels: int = 8, scale: float = 1.2):
+    """A copy of `w` whose edges sit on pyramid levels drawn independently with p(l) ~ 0.75^l (most keypoints come from the
+    fine levels, all levels occur), inv_sigma2 taken per edge from level_inv_sigma2().  -> (window, levels (E,) int32)."""
+    import copy
+    rng = np.random.default_rng(seed)
+    p = 0.75 ** np.arange(n_levels)
+    levels = rng.choice(n_levels, size=w.n_edges, p=p / p.sum()).astype(np.int32)
+    out = copy.deepcopy(w)
+    out.inv_sigma2 = level_inv_sigma2(n_levels, scale)[levels]
+    out.meta = dict(out.meta, level_seed=seed, n_levels=n_levels)
+    return out, levels
+
+
+# ---------------------------------------------------------------------------------------------
 # A change of world frame.  Every generator in this file builds its cameras as small rotations about the identity (a yaw
 # about y, a few hundredths of a radian per axis): quaternions with w ~ 1, rotation matrices with positive trace.  For a rigid
 # motion G = (Rg, tg) the points become X' = Rg X + tg and the poses Tcw' = Tcw o G^-1 (R' = R Rg^T, t' = t - R' tg); the

@@ -191,6 +191,7 @@ def main():
     w = synth.make_window(5, 2, 80, seed=41, run_lo=2, run_hi=5, stereo_frac=0.6)
     save("lba_stereo", w, lm_dense(w))
     cameras()
+    levels()
 
 
 def cameras():
@@ -200,5 +201,13 @@ def cameras():
     save("lba_cameras", w, lm_dense(w))
 
 
+def levels():
+    # every edge weighted by the pyramid level of its keypoint (inv_sigma2 = mvInvLevelSigma2[octave], Optimizer.cc:657-658,
+    # 685-687): cfg("small")'s shape with a tenth of the observations stereo, all eight levels of the 1.2 pyramid
+    w, lv = synth.with_levels(synth.make_window(8, 2, 200, 11, run_lo=2, run_hi=6, stereo_frac=0.1), seed=3)
+    assert (np.bincount(lv, minlength=8) > 0).all() and 0 < (w.obs_right >= 0).sum() < w.n_edges
+    save("lba_levels", w, lm_dense(w))
+
+
 if __name__ == "__main__":
-    cameras() if sys.argv[1:] == ["cameras"] else main()
+    {("cameras",): cameras, ("levels",): levels}.get(tuple(sys.argv[1:]), main)()

@@ -6,8 +6,10 @@ import math
 
 import numpy as np
 
+from movba import synth
+
 N_LEVELS = 8
-SCALE_12 = np.cumprod(np.concatenate([[1.0], np.full(N_LEVELS - 1, 1.2)]))      # mvScaleFactors: 1, 1.2, 1.2 * 1.2, ...
+SCALE_12 = synth.level_scale_factors(N_LEVELS, 1.2, np.float64)      # mvScaleFactors: 1, 1.2, 1.2 * 1.2, ... (in double here)
 SCALE_POW2 = 2.0 ** np.arange(N_LEVELS)
 PARITY_LENGTHS = (0, 1, 2, 63, 64, 65, 255, 256, 257, 300)
 PARITY_VIEWS = 300

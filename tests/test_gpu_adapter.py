@@ -34,8 +34,10 @@ def _f32_pose(p):
     return p.astype(np.float64)
 
 
-def _write_window(path, w, bad_kf=-1):
-    """bad_kf: index of a keyframe the mock map flags bad (KeyFrame::isBad()), -1 = none"""
+def _write_window(path, w, bad_kf=-1, levels=None):
+    """bad_kf: index of a keyframe the mock map flags bad (KeyFrame::isBad()), -1 = none; levels: the pyramid level of every
+    edge's keypoint (cv::KeyPoint::octave; none: level 0 everywhere) - the mock keyframes hold the 1.2 pyramid's
+    mvInvLevelSigma2, synth.level_inv_sigma2()"""
     with open(path, "wb") as f:
         f.write(struct.pack("4i", w.n_poses, w.n_points, w.n_edges, bad_kf + 1))
         f.write(np.ascontiguousarray(w.pose_fixed, np.uint8).tobytes())
@@ -47,12 +49,15 @@ def _write_window(path, w, bad_kf=-1):
         has_cams = getattr(w, "cam_kf", None) is not None
         if getattr(w, "obs_right", None) is not None:
             f.write(struct.pack("d", w.bf)); f.write(np.ascontiguousarray(w.obs_right, np.float64).tobytes())
-        elif has_cams:                                # (the camera trailer sits behind the stereo one)
+        elif has_cams or levels is not None:          # (the camera and octave trailers sit behind the stereo one)
             f.write(struct.pack("d", 0.0)); f.write(np.full(w.n_edges, -1.0).tobytes())
         if has_cams:
             f.write(struct.pack("i", 0x43414d31)); f.write(np.ascontiguousarray(w.cam_kf, np.float64).tobytes())
             bfk = w.bf_kf if getattr(w, "bf_kf", None) is not None else np.zeros(w.n_poses)
             f.write(np.ascontiguousarray(bfk, np.float64).tobytes())
+        if levels is not None:
+            assert len(levels) == w.n_edges
+            f.write(struct.pack("i", 0x4f435431)); f.write(np.ascontiguousarray(levels, np.int32).tobytes())
 
 
 def _read_out(path, w):
@@ -102,21 +107,27 @@ def _local_subwindow(w):
     return sub, used_pose, local_pt, keep_e
 
 
-@pytest.mark.parametrize("name", ["small", "cfg2", "cfg3", "stereo", "cameras", "stereo-cameras"])
+@pytest.mark.parametrize("name", ["small", "cfg2", "cfg3", "stereo", "cameras", "stereo-cameras", "levels"])
 def test_local_bundle_adjustment_through_the_adapter(adapter_bin, oracle_mod, tmp_path, name):
     # "cfg3": the window the headline is quoted on (50 + 10 keyframes x 20 000 map points), map content checked like the small ones
     # "stereo": a window whose keyframes hold stereo observations (mvuRight >= 0, Optimizer.cc:673-705)
     # "cameras": every keyframe with a GeometricCamera (and mbf) of its own, three different ones in the window
     # (e->pCamera = pKFi->mpCamera, Optimizer.cc:664; e->bf = pKFi->mbf, :695)
+    # "levels": keypoints on all eight pyramid levels, the edge's information looked up by octave (Optimizer.cc:657-658); the
+    # oracle solves the window with inv_sigma2 from the same table
+    lv = None
     if name.startswith("stereo"):
         w = synth.make_window(6, 2, 150, seed=43, run_lo=2, run_hi=5, stereo_frac=0.7)
     else:
-        w = synth.cfg("small" if name == "cameras" else name)
+        w = synth.cfg("small" if name in ("cameras", "levels") else name)
     if name.endswith("cameras"):
         w = synth.mixed_cameras(w, seed=44)
+    if name == "levels":
+        w, lv = synth.with_levels(w, seed=1)
+        assert len(np.unique(w.inv_sigma2)) == 8
     w.poses = _f32_pose(w.poses)                     # the doubles the adapter derives from the float map
     fin, fout = str(tmp_path / "w.bin"), str(tmp_path / "o.bin")
-    _write_window(fin, w)
+    _write_window(fin, w, levels=lv)
     subprocess.check_call([adapter_bin, "lba", fin, fout])
     out = _read_out(fout, w)
     sub, used_pose, local_pt, keep_e = _local_subwindow(w)
@@ -197,10 +208,17 @@ def test_adapter_dumps_replayable_windows(adapter_bin, solver, oracle_mod, tmp_p
     """MOVBA_DUMP_DIR: the adapter writes the flattened window it solved; replaying the file through the
     C-ABI gives the same result, and the keyframe-trajectory ATE of GPU and oracle solutions agree (cfg4 harness)."""
     from movba import ate, capture
-    w = synth.cfg("small")
+    _dump_and_replay(adapter_bin, solver, oracle_mod, tmp_path, synth.cfg("small"), None, ate, capture)
+    # ... and a window with keypoints on all eight pyramid levels: the dump and capture.py carry every edge's weight through
+    (tmp_path / "levels").mkdir()
+    w, lv = synth.with_levels(synth.cfg("small"), seed=2)
+    _dump_and_replay(adapter_bin, solver, oracle_mod, tmp_path / "levels", w, lv, ate, capture)
+
+
+def _dump_and_replay(adapter_bin, solver, oracle_mod, tmp_path, w, lv, ate, capture):
     w.poses = _f32_pose(w.poses)
     fin, fout = str(tmp_path / "w.bin"), str(tmp_path / "o.bin")
-    _write_window(fin, w)
+    _write_window(fin, w, levels=lv)
     env = dict(os.environ, MOVBA_DUMP_DIR=str(tmp_path))
     subprocess.check_call([adapter_bin, "lba", fin, fout], env=env)
     dumped = capture.load_window(str(tmp_path / "lba_000000.mbw"))
@@ -209,6 +227,12 @@ def test_adapter_dumps_replayable_windows(adapter_bin, solver, oracle_mod, tmp_p
     np.testing.assert_array_equal(dumped.poses, sub.poses)
     # map points arrive in the adapter's first-seen order (Optimizer.cc:479-504), not by id: same multiset of edges
     np.testing.assert_array_equal(np.sort(dumped.obs.ravel()), np.sort(sub.obs.ravel()))
+    # ... each with its own weight: an edge is known by its keyframe and its observation
+    rows = lambda x: np.stack([x.edge_pose.astype(np.float64), x.obs[:, 0], x.obs[:, 1], x.inv_sigma2], 1)
+    a, b = rows(dumped), rows(sub)
+    assert len(np.unique(b[:, :3], axis=0)) == sub.n_edges
+    np.testing.assert_array_equal(a[np.lexsort(a[:, 2::-1].T)], b[np.lexsort(b[:, 2::-1].T)])
+    assert len(np.unique(dumped.inv_sigma2)) == (1 if lv is None else 8)
     r, o = solver.solve(dumped), oracle_mod.solve(dumped)
     assert np.abs(r["poses"] - o["poses"]).max() < 1e-8
     # ATE of the optimised keyframe trajectory against the generating truth: GPU within 1e-6 relative of the oracle
@@ -269,12 +293,22 @@ def test_local_bundle_adjustment_with_a_bad_observer(adapter_bin, oracle_mod, tm
     """A fixed keyframe flagged bad (KeyFrame::isBad(), Optimizer.cc:515): it gets no vertex and its observations no edges,
     so some local points have fewer edges than observations — the flattener's gap-closing path — and the result is the
     optimum of the window without those edges; the bad keyframe itself is left alone."""
-    w = synth.cfg("small")
+    _bad_observer(adapter_bin, oracle_mod, tmp_path, synth.cfg("small"), None)
+
+
+def test_local_bundle_adjustment_with_a_bad_observer_and_level_weights(adapter_bin, oracle_mod, tmp_path):
+    """The same with keypoints on all eight pyramid levels: closing the gaps moves inv_sigma2 along with the observations
+    (Optimizer.cc:685-699); an edge left with a neighbour's weight gives another optimum (tests/test_level_weights_cpu.py)."""
+    w, lv = synth.with_levels(synth.cfg("small"), seed=2)
+    _bad_observer(adapter_bin, oracle_mod, tmp_path, w, lv)
+
+
+def _bad_observer(adapter_bin, oracle_mod, tmp_path, w, lv):
     w.poses = _f32_pose(w.poses)
     fixed_idx = np.flatnonzero(w.pose_fixed == 1)
     b = int(fixed_idx[np.argmax(np.bincount(w.edge_pose, minlength=w.n_poses)[fixed_idx])])
     fin, fout = str(tmp_path / "w.bin"), str(tmp_path / "o.bin")
-    _write_window(fin, w, bad_kf=b)
+    _write_window(fin, w, bad_kf=b, levels=lv)
     subprocess.check_call([adapter_bin, "lba", fin, fout])
     out = _read_out(fout, w)
     keep = w.edge_pose != b

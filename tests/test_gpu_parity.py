@@ -41,7 +41,7 @@ def check_against(r, o, w, rot=ROT_TOL, trans=TRANS_TOL, point=POINT_TOL, noise_
     assert np.abs(r["poses"][fx] - o["poses"][fx]).max() < 1e-15
 
 
-@pytest.mark.parametrize("name", ["lba_tiny", "lba_small", "lba_hard", "lba_norobust", "lba_stereo", "lba_cameras"])
+@pytest.mark.parametrize("name", ["lba_tiny", "lba_small", "lba_hard", "lba_norobust", "lba_stereo", "lba_cameras", "lba_levels"])
 def test_golden_fixtures(solver, oracle_mod, name):
     w, g = load_golden(name)
     r = solver.solve(w)
@@ -282,7 +282,7 @@ def test_stereo_edges(solver, oracle_mod, frac):
     assert np.abs(solver.solve(wm)["poses"] - r["poses"]).max() > 1e-6
 
 
-@pytest.mark.parametrize("name", ["small", "cfg2", "cfg3", "stereo", "ragged", "150kf", "descending-150kf", "400kf"])
+@pytest.mark.parametrize("name", ["small", "cfg2", "cfg3", "stereo", "ragged", "150kf", "descending-150kf", "400kf", "levels"])
 def test_device_structure_pass_equals_host_structure_pass(solver, built_lib, name):
     """The per-pair entry lists are counted and filled on the GPU (struct_kernels.hip up to 80 free keyframes, the sort-based
     pass of struct_sort.hip beyond: "150kf", "400kf"); the test build's hook `host_structure` forces the host builder.  Same
@@ -300,6 +300,8 @@ def test_device_structure_pass_equals_host_structure_pass(solver, built_lib, nam
         # observers of a point in descending keyframe order (the reference's std::map<KeyFrame*> order is arbitrary)
         order = np.lexsort((-w.edge_pose, w.edge_point))
         w.edge_pose, w.edge_point, w.obs, w.inv_sigma2 = w.edge_pose[order], w.edge_point[order], w.obs[order], w.inv_sigma2[order]
+    elif name == "levels":
+        w, _ = synth.with_levels(synth.cfg("cfg2"), seed=1)           # inv_sigma2 by pyramid level: tests/test_level_weights_cpu.py
     else:
         w = synth.cfg(name)
     a = solver.solve(w)
@@ -315,7 +317,7 @@ def test_device_structure_pass_equals_host_structure_pass(solver, built_lib, nam
 
 
 @pytest.mark.parametrize("name", ["small", "cfg2", "cfg3", "stereo", "ragged", "shuffled", "free-keyframe-without-edges", "ungrouped", "points-nobody-observes",
-                                  "beyond-the-scans-register-segments"])
+                                  "beyond-the-scans-register-segments", "levels"])
 def test_device_grouping_pass_equals_host_grouping_pass(solver, built_lib, name):
     """Validation, the points' edge ranges, edges per keyframe, hessian indices and pose-major slots - structure.cpp's build_basic,
     one pass over the caller's edges on the calling thread - are made on the GPU for the windows whose pair structure the device
@@ -347,6 +349,8 @@ def test_device_grouping_pass_equals_host_grouping_pass(solver, built_lib, name)
         w = synth.cfg("cfg2")
         keep = ~np.isin(w.edge_point, [0, 7, 8, 9, w.n_points - 1])
         w.edge_pose, w.edge_point, w.obs, w.inv_sigma2 = w.edge_pose[keep], w.edge_point[keep], w.obs[keep], w.inv_sigma2[keep]
+    elif name == "levels":
+        w, _ = synth.with_levels(synth.cfg("cfg2"), seed=1)
     else:
         w = synth.cfg(name)
     a = solver.solve(w)
@@ -362,13 +366,16 @@ def test_device_grouping_pass_equals_host_grouping_pass(solver, built_lib, name)
     assert np.array_equal(a["trace"]["pcg"], b["trace"]["pcg"]) and np.array_equal(a["trace"]["f1"], b["trace"]["f1"])
 
 
-@pytest.mark.parametrize("name", ["cfg2", "cfg3", "stereo"])
+@pytest.mark.parametrize("name", ["cfg2", "cfg3", "stereo", "levels"])
 def test_input_arrays_in_the_librarys_pinned_memory_are_read_where_they_lie(built_lib, solver, name):
     """A caller that flattens its window into movba_host_alloc memory (the adapter does): the device reads the index arrays out
     of it and the copy engine takes observations and estimates straight from it - nothing is staged.  Same bits as the same
     window handed over in ordinary memory, call after call, and the caller's arrays are its own again when the call returns
     (overwritten with garbage between calls here)."""
-    w = synth.make_window(12, 3, 1500, seed=57, run_lo=2, run_hi=7, stereo_frac=0.5) if name == "stereo" else synth.cfg(name)
+    if name == "levels":
+        w, _ = synth.with_levels(synth.cfg("cfg2"), seed=1)
+    else:
+        w = synth.make_window(12, 3, 1500, seed=57, run_lo=2, run_hi=7, stereo_frac=0.5) if name == "stereo" else synth.cfg(name)
     ref = solver.solve(w)
     s = built_lib.Solver()
     try:

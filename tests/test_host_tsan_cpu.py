@@ -51,14 +51,16 @@ def test_adapter_under_address_and_undefined_behaviour_sanitizers(tmp_path):
         assert "ERROR: AddressSanitizer" not in p.stderr and "runtime error:" not in p.stderr, p.stderr[:4000]
         assert p.returncode == 0, p.stderr[-2000:]
 
-    cases = [("lba", synth.cfg("small"), -1), ("lba", synth.cfg("cfg2"), -1),
-             ("lba", synth.mixed_cameras(synth.make_window(6, 2, 150, seed=43, run_lo=2, run_hi=5, stereo_frac=0.7), seed=44), -1),
-             ("lba", synth.cfg("small"), 1),
-             ("gba", synth.cfg("small"), -1)]
-    for k, (mode, w, bad) in enumerate(cases):
+    # (the window with a bad observer has its keypoints on all eight pyramid levels: the octave trailer of the window file)
+    levelled, levels = synth.with_levels(synth.cfg("small"), seed=2)
+    cases = [("lba", synth.cfg("small"), -1, None), ("lba", synth.cfg("cfg2"), -1, None),
+             ("lba", synth.mixed_cameras(synth.make_window(6, 2, 150, seed=43, run_lo=2, run_hi=5, stereo_frac=0.7), seed=44), -1, None),
+             ("lba", levelled, 1, levels),
+             ("gba", synth.cfg("small"), -1, None)]
+    for k, (mode, w, bad, lv) in enumerate(cases):
         w.poses = ga._f32_pose(w.poses)
         fin = str(tmp_path / f"w{k}.bin")
-        ga._write_window(fin, w, bad_kf=bad)
+        ga._write_window(fin, w, bad_kf=bad, levels=lv)
         run(mode, fin)
     f = synth.make_frame(n=300, seed=5)
     fin = str(tmp_path / "pose.bin")

@@ -50,7 +50,7 @@ def make_pair(n_used, scene="general", seed=0, mismatch=0.0, mask=False, negate=
     pair = dict(obs1=tv["obs1"], obs2=tv["obs2"], points=X0, pose2=np.concatenate([synth.quat_from_R(R0), t0]), cam=tv["cam"],
                 min_tracked=min_tracked, max_iters=max_iters, huber_delta=huber)
     if sigmas:
-        lv = 1.2 ** rng.integers(0, 4, (2, n_used))
+        lv = synth.level_scale_factors(4, 1.2, np.float64)[rng.integers(0, 4, (2, n_used))]
         pair["inv_sigma2_1"], pair["inv_sigma2_2"] = 1.0 / lv[0] ** 2, 1.0 / lv[1] ** 2
     if mask:
         pair = spread_out(pair, seed)

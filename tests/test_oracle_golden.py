@@ -8,7 +8,8 @@ import pytest
 
 from conftest import load_golden, quat_angle
 
-CASES = ["lba_tiny", "lba_small", "lba_hard", "lba_norobust", "lba_stereo", "lba_cameras"]     # lba_cameras: a camera per keyframe
+CASES = ["lba_tiny", "lba_small", "lba_hard", "lba_norobust", "lba_stereo", "lba_cameras",     # lba_cameras: a camera per keyframe
+         "lba_levels"]                                                                          # lba_levels: inv_sigma2 by pyramid level
 
 
 @pytest.mark.parametrize("name", CASES)
