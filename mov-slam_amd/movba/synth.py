@@ -474,6 +474,61 @@ def regauge_triangulation(sc: dict, Rg, tg=(0.0, 0.0, 0.0), flip_every: int = 0)
     return out
 
 
+# ---------------------------------------------------------------------------------------------
+# A change of map scale and of world origin.  Every generator in this file puts its cameras within a few metres of the origin,
+# its points 4 - 30 units deep and its baselines at 0.3 units.  A monocular map is rescaled to median depth 1 when it is made
+# (movba_init_map), and a trajectory runs hundreds of units away from where it started.  For X' = s X + c the poses keep R and
+# get t' = s t - R c; every length scales with s, a stereo baseline (bf, bf_kf) among them; observations, weights and cameras
+# stay.  It is the same optimisation problem in other units - but not the same LM path when s != 1: the damping lambda I is
+# not scale-covariant.  Made in double, nothing rounded to float32 again (as regauge).  unsimilarity_* map results back.
+# ---------------------------------------------------------------------------------------------
+def similarity_points(X, s: float, c=(0.0, 0.0, 0.0)):
+    return s * np.asarray(X, np.float64) + np.asarray(c, np.float64)
+
+
+def similarity_poses(poses, s: float, c=(0.0, 0.0, 0.0)):
+    """(N, 7) poses Tcw in the world X' = s X + c: the quaternions as they are, t' = s t - R c."""
+    out = np.array(poses, np.float64)
+    c = np.asarray(c, np.float64)
+    for i, p in enumerate(out):
+        out[i, 4:] = s * p[4:] - R_from_quat(p[:4] / np.linalg.norm(p[:4])) @ c
+    return out
+
+
+def unsimilarity_points(X, s: float, c=(0.0, 0.0, 0.0)):
+    """a result of the transformed problem in the generator's world: X = (X' - c) / s"""
+    return (np.asarray(X, np.float64) - np.asarray(c, np.float64)) / s
+
+
+def unsimilarity_poses(poses, s: float, c=(0.0, 0.0, 0.0)):
+    """... t = (t' + R c) / s"""
+    out = np.array(poses, np.float64)
+    c = np.asarray(c, np.float64)
+    for i, p in enumerate(out):
+        out[i, 4:] = (p[4:] + R_from_quat(p[:4] / np.linalg.norm(p[:4])) @ c) / s
+    return out
+
+
+def similarity(w: Window, s: float, c=(0.0, 0.0, 0.0)) -> Window:
+    """The window `w` in the world X' = s X + c: estimates, truth and stereo baselines follow, everything else is shared."""
+    import dataclasses
+    meta = dict(w.meta); meta["similarity"] = (float(s), tuple(float(v) for v in c))
+    return dataclasses.replace(
+        w, poses=similarity_poses(w.poses, s, c), points=similarity_points(w.points, s, c),
+        truth_poses=None if w.truth_poses is None else similarity_poses(w.truth_poses, s, c),
+        truth_points=None if w.truth_points is None else similarity_points(w.truth_points, s, c),
+        bf=s * w.bf, bf_kf=None if w.bf_kf is None else s * np.asarray(w.bf_kf, np.float64), meta=meta)
+
+
+def similarity_frame(f: dict, s: float, c=(0.0, 0.0, 0.0)) -> dict:
+    """A make_frame() operand in the world X' = s X + c: Xw, pose0 and truth follow."""
+    out = dict(f)
+    out["Xw"] = similarity_points(f["Xw"], s, c)
+    out["pose0"] = similarity_poses(f["pose0"][None], s, c)[0]
+    out["truth"] = similarity_poses(f["truth"][None], s, c)[0]
+    return out
+
+
 def pattern_cfg(name: str, seed: int | None = None) -> Window:
     """cfg3-sized windows (50 + 10 keyframes x 20 000 map points) of the other covisibility patterns."""
     if name == "hub":

@@ -146,13 +146,17 @@ def usual(w):
     return dict(DEGENERATE_TOL if least < 3 else WEAK_TOL if least < 12 else MODULE_TOL)
 
 
-def tolerances(w, sp, factor=3):
+def tolerances(w, sp, factor=3, length_unit=1.0):
     """check_against's keyword arguments for window w with measured spread sp: max(usual, factor * spread) per quantity.
     A factor at all, because a maximum over a finite sample underestimates the reach of the distribution and because the GPU
     differs from the oracle by more than within-point order (other reduction trees in the Schur pass, another reduced solver);
-    3 is the factor the pose bounds have had since they were first measured.  It is not a knob for making a case pass."""
+    3 is the factor the pose bounds have had since they were first measured.  It is not a knob for making a case pass.
+    length_unit: the size of w's map in units of the generators' (synth.similarity's s).  The usual translation and point
+    tolerances are statements about a map of the generators' size and are multiplied by it; rotation, lambda, F1 and chi2 have
+    no length in them and stay."""
     u = usual(w)
     s = factor * sp.chi2
-    return dict(rot=max(u["rot"], factor * sp.rot), trans=max(u["trans"], factor * sp.trans), point=max(u["point"], factor * sp.point),
+    return dict(rot=max(u["rot"], factor * sp.rot), trans=max(length_unit * u["trans"], factor * sp.trans),
+                point=max(length_unit * u["point"], factor * sp.point),
                 lam_rtol=max(USUAL_LAM, factor * sp.lam), f1_rtol=max(USUAL_F1, factor * sp.f1),
                 chi2_tol=USUAL_CHI2 if s <= USUAL_CHI2[0] else (s, s / 10))
