@@ -182,6 +182,88 @@ unsigned long long *host_block_view(const void *p, size_t bytes)
 
 }  // namespace movba
 
+#ifdef MOVBA_CLOCK_STAMP
+// Host side of the diagnostic build's clock stamps (clock_stamp.h), all of it: the handle's stamp buffer - the pose call's
+// segment slots first, then the window's segment slots and records - its report lines, and the one function that hands a
+// run's records to the caller (declared by the scripts that call it, not by include/movba.h).
+namespace movba {
+
+static size_t stamp_words(const StampBuf &b) { return (size_t)b.n_seg + 8 * ((size_t)b.n_rec[kStampPoint] + (size_t)b.n_rec[kStampSchur]); }
+
+// the uploaded window's part: capacities from the grids its launches use (launch_backsub, launch_schur), zeroed.  Called at the
+// upload and again at the start of every run of the window, solo or in a batch (where k_init_pose used to zero Ctrl's words):
+// a run's report and records are its own
+int stamp_window(movba_handle *h)
+{
+    if (h->early_status != MOVBA_OK) return MOVBA_OK;
+    DevWindow &w = h->win;
+    StampBuf b{};
+    b.n_seg = kSegSlots;
+    b.n_rec[kStampPoint] = w.n_pt_blocks + 1;
+    b.n_rec[kStampSchur] = w.nitems > 0 ? schur_blocks(w) * kSchurWaves : 0;
+    const int rc = h->stamp.grow(h, sizeof(unsigned long long) * (kPoseSegSlots + stamp_words(b))); if (rc) return rc;
+    b.words = reinterpret_cast<unsigned long long *>(h->stamp.p) + kPoseSegSlots;
+    HIP_TRY(hipMemsetAsync(b.words, 0, sizeof(unsigned long long) * stamp_words(b), h->stream));
+    w.stamp = b;
+    return MOVBA_OK;
+}
+
+int stamp_pose(movba_handle *h, PoseDev &p)
+{
+    const int rc = h->stamp.grow(h, sizeof(unsigned long long) * kPoseSegSlots); if (rc) return rc;
+    p.stamp = StampBuf{};
+    p.stamp.words = reinterpret_cast<unsigned long long *>(h->stamp.p);
+    p.stamp.n_seg = kPoseSegSlots;
+    HIP_TRY(hipMemsetAsync(p.stamp.words, 0, sizeof(unsigned long long) * kPoseSegSlots, h->stream));
+    return MOVBA_OK;
+}
+
+void stamp_report_run(movba_handle *h)
+{
+    unsigned long long s[kSegSlots];
+    if (!h->win.stamp.words || hipMemcpy(s, h->win.stamp.words, sizeof(s), hipMemcpyDeviceToHost) != hipSuccess) return;
+    const double iters = h->ctrl_host->pcg_total_iters ? h->ctrl_host->pcg_total_iters : 1, solves = h->ctrl_host->n_solves ? h->ctrl_host->n_solves : 1;
+    std::fprintf(stderr, "libmovba[stamp]: k_pcg_rows %llu shader cycles in %llu x 10 ns -> %.3f GHz\n", s[kSegCycles], s[kSegTicks],
+                 s[kSegTicks] ? 0.1 * (double)s[kSegCycles] / (double)s[kSegTicks] : 0.0);
+    std::fprintf(stderr, "libmovba[stamp]: per-iteration segments (wave 0, cycles):");
+    for (int k = 0; k < 8; ++k) std::fprintf(stderr, " s%d=%.0f", k, (double)s[kSegIter + k] / iters);
+    for (int wv = 0; wv < 8; ++wv) {
+        std::fprintf(stderr, "\nlibmovba[stamp]:   wave %d:", wv);
+        for (int k = 0; k < 8; ++k) std::fprintf(stderr, " s%d=%.0f", k, (double)s[kSegWave + 8 * wv + k] / iters);
+    }
+    std::fprintf(stderr, "\nlibmovba[stamp]: setup phases per launch (cycles):");
+    for (int k = 0; k < 8; ++k) std::fprintf(stderr, " p%d=%.0f", k, (double)s[kSegPhase + k] / solves);
+    std::fprintf(stderr, "\n");
+}
+
+void stamp_report_pose(movba_handle *h, int lm_iters)
+{
+    unsigned long long s[kPoseSegSlots];
+    if (hipMemcpy(s, h->stamp.p, sizeof(s), hipMemcpyDeviceToHost) != hipSuccess) return;
+    std::fprintf(stderr, "libmovba[stamp]: k_pose_opt, cycles per LM iteration (%d): system pass %.0f, reduction of 28 %.0f, solve + update %.0f, cost pass + reduction %.0f\n",
+                 lm_iters, (double)s[0] / lm_iters, (double)s[1] / lm_iters, (double)s[2] / lm_iters, (double)s[3] / lm_iters);
+}
+
+}  // namespace movba
+
+// The records of one class (0: the back-substitution pass, per workgroup; 1: k_schur, per wave; 2: the segment slots, eight to a
+// record) that the handle's last run left: up to `cap` records of eight words into `out`.  Returns how many records the class
+// has - its launch grid - or an error.
+extern "C" int movba_stamp_records(movba_handle *h, int cls, unsigned long long *out, int cap)
+{
+    if (!h || cls < 0 || (cls >= kStampClasses && cls != kStampSegments) || cap < 0 || (cap > 0 && !out)) return MOVBA_ERR_ARG;
+    const StampBuf &b = h->win.stamp;
+    if (!h->ran || !b.words) return MOVBA_ERR_STATE;
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    const int have = cls == kStampSegments ? b.n_seg / 8 : b.n_rec[cls];
+    const unsigned long long *src = cls == kStampSegments ? b.words : b.words + b.n_seg + 8 * (size_t)(cls == kStampSchur ? b.n_rec[kStampPoint] : 0);
+    const int n = std::min(cap, have);
+    if (n > 0) HIP_TRY(hipMemcpy(out, src, sizeof(unsigned long long) * 8 * (size_t)n, hipMemcpyDeviceToHost));
+    return have;
+}
+#endif
+
 namespace {
 
 // One launch of the one-launch direct solver at a time per device.  Its workgroups wait for one another, which is safe while all
@@ -386,6 +468,7 @@ void movba_destroy(movba_handle *h)
     for (auto &ring : h->batch_phase_ev) for (hipEvent_t e : ring) if (e) (void)hipEventDestroy(e);
     for (void *dev : { (void *)h->ingest_counter, (void *)h->arena }) if (dev) (void)hipFree(dev);
     for (Scratch *b : { &h->scratch, &h->scratch2, &h->pose_scratch, &h->marg, &h->marg_host, &h->batch_dev, &h->batch_host }) b->release();
+    STAMP_HOST(h->stamp.release());
     if (h->stage) (void)hipHostFree(h->stage);
     if (h->hstat) (void)hipHostFree((void *)h->hstat);
     if (h->ctrl_host) (void)hipHostFree(h->ctrl_host);
@@ -659,6 +742,7 @@ int movba_lba_run(movba_handle *h)
     // large as the upload needed, which is more than the results take)
     h->export_in_run = h->export_hint && export_layout(w).end <= h->stage_cap;
     if (!h->export_in_run) for (int k = 0; k < 3; ++k) { h->user_dst[k] = nullptr; h->user_host[k] = nullptr; }
+    STAMP_HOST(const int rs = stamp_window(h); if (rs) return rs);     // (a run's report lines are its own: zeroed here as at the upload)
 
     // One kernel waits for other workgroups INSIDE a launch: the one-launch direct solver (dense_persist.hip).  Its waits are
     // bounded (DevWindow::wait_ticks, 20 ms) and cannot deadlock on an otherwise idle device, but its workgroups are not
@@ -700,19 +784,7 @@ int movba_lba_run(movba_handle *h)
         }
         break;
     }
-#ifdef MOVBA_CLOCK_STAMP
-    std::fprintf(stderr, "libmovba[stamp]: k_pcg_rows %llu shader cycles in %llu x 10 ns -> %.3f GHz\n", h->ctrl_host->dbg_cycles,
-                 h->ctrl_host->dbg_ticks, h->ctrl_host->dbg_ticks ? 0.1 * (double)h->ctrl_host->dbg_cycles / (double)h->ctrl_host->dbg_ticks : 0.0);
-    std::fprintf(stderr, "libmovba[stamp]: per-iteration segments (wave 0, cycles):");
-    for (int k = 0; k < 8; ++k) std::fprintf(stderr, " s%d=%.0f", k, (double)h->ctrl_host->dbg_seg[k] / (h->ctrl_host->pcg_total_iters ? h->ctrl_host->pcg_total_iters : 1));
-    for (int wv = 0; wv < 8; ++wv) {
-        std::fprintf(stderr, "\nlibmovba[stamp]:   wave %d:", wv);
-        for (int k = 0; k < 8; ++k) std::fprintf(stderr, " s%d=%.0f", k, (double)h->ctrl_host->dbg_wseg[wv][k] / (h->ctrl_host->pcg_total_iters ? h->ctrl_host->pcg_total_iters : 1));
-    }
-    std::fprintf(stderr, "\nlibmovba[stamp]: setup phases per launch (cycles):");
-    for (int k = 0; k < 8; ++k) std::fprintf(stderr, " p%d=%.0f", k, (double)h->ctrl_host->dbg_seg2[k] / (h->ctrl_host->n_solves ? h->ctrl_host->n_solves : 1));
-    std::fprintf(stderr, "\n");
-#endif
+    STAMP_HOST(stamp_report_run(h));
     h->ran = true;
     return MOVBA_OK;
 }
@@ -810,6 +882,7 @@ int movba_lba_run_batch(movba_handle *const *hs, int32_t n)
                 movba_handle *h = G.hs[i];
                 h->win.pose_export = (h->pose_export && h->pose_export_cap >= (int64_t)sizeof(double) * 7 * h->win.NP) ? h->pose_export : nullptr;
                 __atomic_store_n(&h->hstat->progress, (uint64_t)0, __ATOMIC_RELAXED); wr_stop(h->hstat, 0); __atomic_store_n(&h->hstat->pause_seq, 0, __ATOMIC_RELAXED);
+                STAMP_HOST(const int rs = stamp_window(h); if (rs) return rs);     // (on the callers' stream, ahead of every group's launches)
                 wins[i] = h->win; wins[i].lds_poses = ldsp ? 1 : 0;
                 pps[i] = run_pcg_params(h);
                 bwv[i] = h->band ? band_arg(h) : -1;

@@ -43,17 +43,6 @@ __device__ __forceinline__ void band_wave_sync()
 
 }  // namespace
 
-#ifdef MOVBA_CLOCK_STAMP
-#define BAND_STAMP(k) do { const unsigned long long _t = __builtin_amdgcn_s_memtime(); if (tid == 0) c->dbg_seg2[k] += _t - stamp_last; stamp_last = _t; } while (0)
-// fine stamps of ONE block step (k == 10), kept in registers and written once at the end; `dep`: a value of the chain the stamp
-// has to stand behind (stamps are scalar instructions, the chain is vector ones)
-#define BAND_FINE(i, dep) do { if (k == 10) { const int d_ = __builtin_amdgcn_readfirstlane(__double2loint(dep)); unsigned long long t_; \
-    asm volatile("s_nop 7\n\ts_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_) : "s"(d_) : "memory"); fine[i] = t_; } } while (0)
-#else
-#define BAND_STAMP(k) do { } while (0)
-#define BAND_FINE(i, dep) do { } while (0)
-#endif
-
 __device__ __forceinline__ void band_body(const DevWindow &w, int bw_arg)
 {
     const int bw = bw_arg & 0xffff;                     // (from bit 16: the test build's park hook, api.cpp band_arg)
@@ -93,10 +82,8 @@ __device__ __forceinline__ void band_body(const DevWindow &w, int bw_arg)
         o_it0[u] = any ? w.pair_item_start[p] : 0; o_it1[u] = any ? w.pair_item_start[p + 1] : 0;
     }
     if (done0) return;
-#ifdef MOVBA_CLOCK_STAMP
-    unsigned long long stamp_last = __builtin_amdgcn_s_memtime();
-    unsigned long long fine[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
-#endif
+    STAMP_SEGMENTS(phase, 8); STAMP_SEG_START(phase);
+    STAMP_SEGMENTS(fine, 8);            // fine stamps of ONE block step (k == 10), each behind a value of the step's dependency chain
     // LDS carve (pcg_plan.cpp: band_lds_bytes): the band, the right-hand side (then z), a second vector (b_p's partner, then x),
     // the step's panel times D, a strip for the reductions, the enumeration of the trailing blocks, two failure words
     double *Lb = sm;                                  // nf x (bw + 1) x 36: block (i, j), i - bw <= j <= i, at band_off(i, j)
@@ -186,7 +173,7 @@ __device__ __forceinline__ void band_body(const DevWindow &w, int bw_arg)
     for (int k = tid; k < n; k += kBT) { const double bb = rhs[k]; w.bp[k] = bb; rhs[k] = bb - aux[k]; }
     __syncthreads();
 
-    BAND_STAMP(0);
+    STAMP_SEG(phase, 0);
     // ---- factorisation S = L D L^T (L unit lower, D diagonal: Cholesky without its square roots), the right-hand side carried
     //      along as one more row (z = D^-1 L^-1 b) ----
     // Step k is ONE sweep over the stacked rows [ D_k ; A_(k+1)k ; ... ; A_(k+m)k ; b_k^T ], one row of six per lane: column by
@@ -257,7 +244,7 @@ __device__ __forceinline__ void band_body(const DevWindow &w, int bw_arg)
         const int m = min(bw, nf - 1 - k);
         double *Lk = Lb + (size_t)k * step_stride;        // what the decoded offsets are relative to
         double v[6];
-        BAND_FINE(0, lambda);
+        STAMP_SEG_START_BEHIND(fine, lambda, k == 10);
         if (sw_first_irel < m) {
             const bool act = s_irel < m;
             double *row = s_irel == -2 ? rhs + 6 * k : Lk + s_off;
@@ -265,7 +252,7 @@ __device__ __forceinline__ void band_body(const DevWindow &w, int bw_arg)
             { const double2 *rp = reinterpret_cast<const double2 *>(row);
               const double2 r0 = rp[0], r1 = rp[1], r2 = rp[2];
               v[0] = r0.x; v[1] = r0.y; v[2] = r1.x; v[3] = r1.y; v[4] = r2.x; v[5] = r2.y; }
-            BAND_FINE(1, v[5]);
+            STAMP_SEG_BEHIND(fine, 1, v[5], k == 10);
             double wu[6];                                   // the row as it stood when its column came up: (L D)
 #pragma unroll
             for (int kk = 0; kk < 6; ++kk) {
@@ -283,7 +270,7 @@ __device__ __forceinline__ void band_body(const DevWindow &w, int bw_arg)
 #pragma unroll
                 for (int q = kk + 1; q < 6; ++q) v[q] = __builtin_fma(-v[kk], cq[q], v[q]);
             }
-            BAND_FINE(2, v[5]);
+            STAMP_SEG_BEHIND(fine, 2, v[5], k == 10);
             if (act && ln >= 6) {
                 double2 *wp = reinterpret_cast<double2 *>(row);
                 wp[0] = make_double2(v[0], v[1]); wp[1] = make_double2(v[2], v[3]); wp[2] = make_double2(v[4], v[5]);
@@ -291,16 +278,16 @@ __device__ __forceinline__ void band_body(const DevWindow &w, int bw_arg)
                 tp[0] = make_double2(wu[0], wu[1]); tp[1] = make_double2(wu[2], wu[3]); tp[2] = make_double2(wu[4], wu[5]);
             }
         }
-        BAND_FINE(3, lambda);
+        STAMP_SEG_BEHIND(fine, 3, lambda, k == 10);
         // L_kk goes over D_k only when every sweeping wave has read D_k (the trailing phase does not touch block (k, k))
         if (m > 0) __syncthreads();
-        BAND_FINE(4, lambda);
+        STAMP_SEG_BEHIND(fine, 4, lambda, k == 10);
         if (wv == 0 && ln < 6) {
             double2 *wp = reinterpret_cast<double2 *>(Lk + s_off);
             wp[0] = make_double2(v[0], v[1]); wp[1] = make_double2(v[2], v[3]); wp[2] = make_double2(v[4], v[5]);
         }
         if (m == 0) break;                                  // (the last step has nothing below it)
-        BAND_STAMP(1);
+        STAMP_SEG(phase, 1);
         // trailing blocks A_ij -= L_ik (L D)_jk^T (i >= j below k in the band) and right-hand side b_i -= L_ik (D z)_k
         auto piece = [&](const double *A, const double *Bq, double *dst, bool is_rhs, bool live) {
             double2 ar[3][3];
@@ -355,10 +342,10 @@ __device__ __forceinline__ void band_body(const DevWindow &w, int bw_arg)
             if (is_rhs) piece(A, T + bw * 36, rhs + 6 * (k + 1 + irel) + a3 * 3, true, true);
             else piece(A, T + jrel * 36 + b3 * 18, Lb + band_off(k + 1 + irel, k + 1 + jrel, bw) + a3 * 18 + b3 * 3, false, true);
         }
-        BAND_FINE(5, lambda);
+        STAMP_SEG_BEHIND(fine, 5, lambda, k == 10);
         __syncthreads();
-        BAND_FINE(6, lambda);
-        BAND_STAMP(2);
+        STAMP_SEG_BEHIND(fine, 6, lambda, k == 10);
+        STAMP_SEG(phase, 2);
     }
     if (tid == 0) { failw[0] = nonfinite; failw[1] = nonpos; }      // (wave 0 sweeps in every step)
     __syncthreads();
@@ -447,7 +434,7 @@ __device__ __forceinline__ void band_body(const DevWindow &w, int bw_arg)
     }
     __syncthreads();
 
-    BAND_STAMP(4);
+    STAMP_SEG(phase, 4);
     // ---- outputs: increment, pose part of computeScale(), trial poses (VertexSE3Expmap::oplusImpl): as the PCG's epilogue ----
     double ps = 0.0;
     for (int r = tid; r < n; r += kBT) {
@@ -473,10 +460,8 @@ __device__ __forceinline__ void band_body(const DevWindow &w, int bw_arg)
         const int h = w.hidx[i];
         store_trial_pose(S1.pose, S1.Rt, i, Tq, h, !fail, aux);
     }
-    BAND_STAMP(5);
-#ifdef MOVBA_CLOCK_STAMP
-    if (tid == 0) for (int i = 0; i < 7; ++i) c->dbg_wseg[0][i] += i ? fine[i] - fine[i - 1] : 0;
-#endif
+    STAMP_SEG(phase, 5);
+    STAMP_SEG_FLUSH(phase, 8, w.stamp, kSegPhase, tid == 0); STAMP_SEG_FLUSH(fine, 8, w.stamp, kSegWave, tid == 0);
     if (tid == 0) {
         w.scale_part[w.n_pt_blocks] = scs;
         c->pcg_fail = fail ? 1 : 0;

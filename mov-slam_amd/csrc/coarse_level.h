@@ -39,12 +39,7 @@ __device__ __forceinline__ void coarse_build(const DevWindow &w, const PcgParams
     int &s_bad = *reinterpret_cast<int *>(gj + 9 * kNC + 2);     // gj: 2 x 4 kNC snapshots + 2 pivots + kNC scaling, then the flag
     const int tid = threadIdx.x;
     const int nf = w.nfree;
-#ifdef MOVBA_CLOCK_STAMP
-    unsigned long long cst_last = __builtin_amdgcn_s_memtime();
-#define COARSE_STAMP(k) do { const unsigned long long _t = __builtin_amdgcn_s_memtime(); if (tid == 0) w.ctrl->dbg_seg2[k] += _t - cst_last; cst_last = _t; } while (0)
-#else
-#define COARSE_STAMP(k) do { } while (0)
-#endif
+    STAMP_SEGMENTS(phase, 8); STAMP_SEG_START(phase);
     // (the schur partials: plain loads; on the two-stream path the caller's waves have made their agent-scope acquire behind
     //  the pass's flags)
     const double *part = w.part, *part_ = part;
@@ -99,7 +94,7 @@ __device__ __forceinline__ void coarse_build(const DevWindow &w, const PcgParams
         }
     }
     __syncthreads();
-    COARSE_STAMP(2);
+    STAMP_SEG(phase, 2);
     // ---- A_c = P^T S P.  Coarse dof (g, d, a): aggregate g, mode d (0: constant, 1: linear in the keyframe index,
     // phi_1(i) = (i - c_g) / h_g), pose component a.  One thread per (coarse block, a, b): it walks the block's fine terms
     // once, in list order, and accumulates the four mode combinations phi_d(i) phi_e(j) together. ----
@@ -227,7 +222,7 @@ __device__ __forceinline__ void coarse_build(const DevWindow &w, const PcgParams
         __syncthreads();
     }
 
-    COARSE_STAMP(3);
+    STAMP_SEG(phase, 3);
     // ---- Gauss-Jordan inverse of the symmetrically scaled matrix D A_c D (unit diagonal), the matrix held in REGISTERS:
     // thread (rg, cg) owns rows 3 rg .. 3 rg + 2 x columns 6 cg .. 6 cg + 5 (32 x 16 threads x 18 elements = 96 x 96).
     // TWO pivots per workgroup barrier (round 4; one until then: 975 cycles per pivot, 39 us per build, most of it the
@@ -335,7 +330,7 @@ __device__ __forceinline__ void coarse_build(const DevWindow &w, const PcgParams
     }
     if (bad && tid == 0) s_bad = 1;
     __syncthreads();
-    COARSE_STAMP(4);
+    STAMP_SEG(phase, 4);
     // ---- publish: A_c^-1 = D (D A_c D)^-1 D for trial+1 and its validity tag ----
     float *dst = w.aci + (size_t)(trial & 1) * kNC * kNC;
 #pragma unroll
@@ -344,7 +339,8 @@ __device__ __forceinline__ void coarse_build(const DevWindow &w, const PcgParams
         for (int q = 0; q < 6; ++q) dst[(3 * rg + r) * kNC + 6 * cg + q] = (float)(t[r][q] * dsc[3 * rg + r] * dsc[6 * cg + q]);
     __syncthreads();
     if (tid == 0) w.aci_tag[trial & 1] = s_bad ? -1 : trial;
-    COARSE_STAMP(5);
+    STAMP_SEG(phase, 5);
+    STAMP_SEG_FLUSH(phase, 8, w.stamp, kSegPhase, tid == 0);
 }
 
 }  // namespace movba

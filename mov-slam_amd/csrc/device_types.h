@@ -6,6 +6,7 @@
 #pragma once
 #include <cstdint>
 
+#include "clock_stamp.h"
 #include "dense_plan.h"
 #include "structure.h"
 
@@ -65,10 +66,6 @@ struct Ctrl {
     int32_t n_sync_timeouts;            // one-launch direct solver: solves in which a workgroup gave up waiting for another (dense_persist.hip)
     int32_t n_band;                     // trials solved by the single-workgroup banded factorisation (band_kernel.hip)
     int32_t pad_c[1];
-    // diagnostic build only (-DMOVBA_CLOCK_STAMP): shader cycles / 100 MHz ticks spent in k_pcg_rows
-    unsigned long long dbg_cycles, dbg_ticks, dbg_seg[8], dbg_seg2[8], dbg_wseg[8][8];
-    unsigned long long dbg_xs[8];       // two-stream path, 10 ns ticks: [0] time of the schur pass's last item flag of the trial (atomic max), then sums over the
-                                        // trials of: [1] last flag -> partials in registers, [2] -> CG starts, [3] -> CG ends, [4] -> done word stored; [5] trials
 };
 
 // Written by k_decide into pinned host memory so the host can keep the queue fed
@@ -190,6 +187,9 @@ struct DevWindow {
     // marks the solve - Ctrl::n_sync_timeouts - and the host runs it again on the paths that wait for nothing; MOVBA_TEST_WAIT_TICKS
     // shortens the first attempt's bound so that tests can see that happen)
     unsigned long long wait_ticks;      // bound of the waits inside the one-launch direct solver (10 ns ticks; 20 ms)
+#ifdef MOVBA_CLOCK_STAMP
+    StampBuf stamp;                     // diagnostic build only, behind everything the product build has (clock_stamp.h)
+#endif
 };
 
 // Device view of the structure pass (struct_kernels.hip)

@@ -250,6 +250,9 @@ struct movba_handle {
     hipEvent_t batch_ev[movba::kMaxGroups + 1] = {};    // [0]: fork from the callers' stream, [g]: join of group g
     hipEvent_t batch_phase_ev[movba::kMaxGroups][movba::kPhaseEvents] = {};     // ring: end of group g's schur launch of trial t (t mod 16)
     movba::Scratch pose_scratch;        // device scratch of the side calls (begin_side_call)
+#ifdef MOVBA_CLOCK_STAMP
+    movba::Scratch stamp;               // diagnostic build only: the clock stamps' buffer (api.cpp: stamp_window, stamp_pose)
+#endif
     // movba_lba_marginals (marginals.cpp): device scratch (controller, factor inverses, W, sigma, outputs) and the pinned image of
     // the outputs; the uploaded window's fixed flags (fixed keyframes get zero blocks)
     movba::Scratch marg, marg_host{nullptr, 0, movba::Scratch::Pinned};

@@ -53,8 +53,6 @@ __device__ __forceinline__ void init_pose_body(const DevWindow &w, int bid, int 
         c->n_pause = 0; c->n_direct = 0; c->n_chol_fail = 0; c->n_band = 0; c->n_sync_timeouts = 0;
         w.aci_tag[0] = -1; w.aci_tag[1] = -1;
         w.ac_prev[kCoarseDim * kCoarseDim + 1] = -1.0;
-        c->dbg_cycles = 0; c->dbg_ticks = 0;
-        for (int k = 0; k < 8; ++k) { c->dbg_seg[k] = 0; c->dbg_seg2[k] = 0; for (int q = 0; q < 8; ++q) c->dbg_wseg[k][q] = 0; }
     }
     if (i >= w.NP) return;
     double q[7];
@@ -216,13 +214,8 @@ __device__ __forceinline__ void point_body(const DevWindow &w, int bid)
 {
     extern __shared__ __attribute__((aligned(16))) double sm[];
     const Ctrl *c = w.ctrl;
-#ifdef MOVBA_CLOCK_STAMP
-    unsigned long long pst[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
-    pst[0] = __builtin_amdgcn_s_memrealtime();
-#define PSTAMP(k) do { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); pst[k] = __builtin_amdgcn_s_memrealtime(); } while (0)
-#else
-#define PSTAMP(k) do { } while (0)
-#endif
+    STAMP_RECORD(pst);
+    STAMP_GATE(pst, c);
     // (the map point's edge range does not depend on the LM state: requested together with the controller's words, one cold
     //  round trip instead of two in a row)
     const int sub = threadIdx.x & (kPointGroup - 1);
@@ -233,19 +226,12 @@ __device__ __forceinline__ void point_body(const DevWindow &w, int bid)
     if (c->done) return;
     const int cur = c->cur;
     if (bid >= w.n_pt_blocks) {         // the pass's extra workgroup: its first wave takes the LM decision (back-substitution passes only)
-#ifdef MOVBA_CLOCK_STAMP
-        const int ns0 = c->n_solves;
-#endif
         if (BACKSUB && bid == w.n_pt_blocks && threadIdx.x < 64) decide_body(w, cur);
-#ifdef MOVBA_CLOCK_STAMP
-        if (BACKSUB && threadIdx.x == 0 && ns0 == 3 && 20000 + 8 * ((size_t)bid + 1) <= (size_t)w.E) {      // (stamps live in the chi2 array: windows large enough only)
-            unsigned long long *dbg = reinterpret_cast<unsigned long long *>(w.out_chi2) + 20000 + 8 * (size_t)bid;
-            dbg[0] = pst[0]; dbg[1] = __builtin_amdgcn_s_memrealtime(); dbg[7] = 2;
-        }
-#endif
+        STAMP_TICKS(pst, 1); STAMP_WORD(pst, 7, 2);
+        STAMP_STORE(pst, w.stamp, kStampPoint, bid, BACKSUB && threadIdx.x == 0);
         return;
     }
-    PSTAMP(1);
+    STAMP_READ(pst, 1);
     const int dst = BACKSUB ? (cur ^ 1) : cur;
     const double lambda = c->lambda;
     const DevState &S0 = w.st[cur];
@@ -342,7 +328,7 @@ __device__ __forceinline__ void point_body(const DevWindow &w, int bid)
         __syncthreads();
     }
 
-    PSTAMP(2);
+    STAMP_READ(pst, 2);
     double scale = 0.0;
     if (BACKSUB) {
         double a0 = 0.0, a1 = 0.0, a2 = 0.0;
@@ -419,7 +405,7 @@ __device__ __forceinline__ void point_body(const DevWindow &w, int bid)
         }
     }
 
-    PSTAMP(3);
+    STAMP_READ(pst, 3);
     // ---- evaluate at the destination state ----
     double h0 = 0, h1 = 0, h2 = 0, h3 = 0, h4 = 0, h5 = 0, v0 = 0, v1 = 0, v2 = 0, F = 0.0;
     const double dsqr = w.huber_delta * w.huber_delta;
@@ -491,7 +477,7 @@ __device__ __forceinline__ void point_body(const DevWindow &w, int bid)
         if (BACKSUB) { S1.point[3 * l] = X[0]; S1.point[3 * l + 1] = X[1]; S1.point[3 * l + 2] = X[2]; }
         if (end > begin) hmax = fmax(fabs(h0), fmax(fabs(h3), fabs(h5)));
     }
-    PSTAMP(4);
+    STAMP_READ(pst, 4);
     if (BACKSUB) {
         // cost and scale partials of the workgroup behind ONE barrier (the sums in block_reduce's order)
         constexpr int NWV = kPointBlock / 64;
@@ -508,15 +494,8 @@ __device__ __forceinline__ void point_body(const DevWindow &w, int bid)
             const unsigned tag = (unsigned)c->n_solves + 1u;
             const __amdgpu_buffer_rsrc_t rr = hx_rsrc(w.dec_rec, 32u * (unsigned)w.n_pt_blocks);
             hx_st_tagged(rr, 2u * (unsigned)bid, Fsum, tag); hx_st_tagged(rr, 2u * (unsigned)bid + 1u, ssum, tag);
-#ifdef MOVBA_CLOCK_STAMP
-            if (c->n_solves == 3 && 20000 + 8 * ((size_t)bid + 1) <= (size_t)w.E) {
-                PSTAMP(5);
-                unsigned long long *dbg = reinterpret_cast<unsigned long long *>(w.out_chi2) + 20000 + 8 * (size_t)bid;
-                for (int k = 0; k < 6; ++k) dbg[k] = pst[k];
-                dbg[6] = ((unsigned long long)__builtin_amdgcn_s_getreg(63492)) | ((unsigned long long)__builtin_amdgcn_s_getreg(63508) << 32);
-                dbg[7] = 1;
-            }
-#endif
+            STAMP_READ(pst, 5); STAMP_WORD(pst, 6, stamp_hw_id()); STAMP_WORD(pst, 7, 1);
+            STAMP_STORE(pst, w.stamp, kStampPoint, bid, true);
         }
     } else {
         const double Fsum = block_reduce<kPointBlock / 64, false>(F, red);
@@ -701,13 +680,7 @@ constexpr int kSchurBatchOff = MOVBA_SCHUR_BO;      // same, off-diagonal items
 template <int NR, bool HPP_ONLY, bool PERKF = false>
 __device__ __forceinline__ void schur_body(const DevWindow &w, int bid)
 {
-#ifdef MOVBA_CLOCK_STAMP
-    unsigned long long wst[5];
-    wst[0] = __builtin_amdgcn_s_memrealtime();
-#define WSTAMP(k) do { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); wst[k] = __builtin_amdgcn_s_memrealtime(); } while (0)
-#else
-#define WSTAMP(k) do { } while (0)
-#endif
+    STAMP_RECORD(wst);
     const int lane = threadIdx.x & 63;
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);       // wave-uniform: item, poses and rotations live in SGPRs
     // XCD-aware launch schedule (structure.cpp): workgroups b, b+8, ... share an XCD (and its L2) and take the slots of
@@ -717,6 +690,7 @@ __device__ __forceinline__ void schur_body(const DevWindow &w, int bid)
     const SchedItem it = w.sched[wg * kSchurWaves + wv];    // this wave's slot: its share of an item one, two or four waves take
     const Ctrl *c = w.ctrl;
     if (c->done) return;
+    STAMP_GATE(wst, c);
     const int sub = it.sub & 0xff, nsub = it.sub >> 8;
     __shared__ __attribute__((aligned(16))) double strips[kSchurWaves][54 * 16];
     __shared__ double wsum[kSchurWaves][64];
@@ -735,7 +709,7 @@ __device__ __forceinline__ void schur_body(const DevWindow &w, int bid)
     for (int k = 0; k < 9; ++k) { Ri[k] = S0.Rt[12 * ip + k]; Rj[k] = S0.Rt[12 * jp + k]; }
     const Cam cmi = cam_of<PERKF>(w, ip), cmj = cam_of<PERKF>(w, jp);
     double *out = w.part + (size_t)item * kPartStride;
-    WSTAMP(1);
+    STAMP_READ(wst, 1);
 
     // Every batch issues the gathers of B entries per lane level by level (entry -> edge records -> point block) before
     // any arithmetic: the loop is a chain of dependent L2 / fabric round trips, not bandwidth.
@@ -783,7 +757,7 @@ __device__ __forceinline__ void schur_body(const DevWindow &w, int bid)
         for (int k = 0; k < 21; ++k) { all[k] = sa[k]; all[27 + k] = ha[k]; }
 #pragma unroll
         for (int k = 0; k < 6; ++k) { all[21 + k] = ca[k]; all[48 + k] = ba[k]; }
-        WSTAMP(2);
+        STAMP_READ(wst, 2);
         wsum[wv][lane] = wave_reduce<54>(all, strip, lane);
     } else {
         constexpr int B = kSchurBatchOff;
@@ -814,10 +788,10 @@ __device__ __forceinline__ void schur_body(const DevWindow &w, int bid)
             for (int u = 0; u < B; ++u)
                 schur_offdiag_entry<NR>(cmi, cmj, ri[u], rj[u], ok[u] ? ri[u].w * rj[u].w : 0.0, sti[u], stj[u], Ri, Rj, h[u], lambda, acc);
         }
-        WSTAMP(2);
+        STAMP_READ(wst, 2);
         wsum[wv][lane] = wave_reduce<36>(acc, strip, lane);
     }
-    WSTAMP(3);
+    STAMP_READ(wst, 3);
     __syncthreads();
     if (active && sub == 0) {
         double t = wsum[wv][lane];
@@ -850,16 +824,8 @@ __device__ __forceinline__ void schur_body(const DevWindow &w, int bid)
             if (it.dst_b >= 0) *(w.img_b + it.dst_b + (size_t)((lane % 6) * 6 + lane / 6) * kPcgRowsThreads) = t;
         }
     }
-#ifdef MOVBA_CLOCK_STAMP
-    WSTAMP(4);
-    if (!HPP_ONLY && lane == 0 && c->n_solves == 3 && 8 * ((size_t)(bid * kSchurWaves + wv) + 1) <= (size_t)w.E) {        // one launch: per-wave stamps (100 MHz ticks), read back through out_chi2
-        unsigned long long *dbg = reinterpret_cast<unsigned long long *>(w.out_chi2) + 8 * (size_t)(bid * kSchurWaves + wv);
-        for (int k = 0; k < 5; ++k) dbg[k] = wst[k];
-        dbg[5] = (unsigned long long)(wend - wbeg);
-        dbg[6] = (unsigned long long)is_diag | ((unsigned long long)__builtin_amdgcn_s_getreg(63492) << 8) | ((unsigned long long)__builtin_amdgcn_s_getreg(63508) << 40);
-        dbg[7] = 1;
-    }
-#endif
+    STAMP_READ(wst, 4); STAMP_WORD(wst, 5, wend - wbeg); STAMP_WORD(wst, 6, (unsigned long long)is_diag | (stamp_hw_id() << 8)); STAMP_WORD(wst, 7, 1);
+    STAMP_STORE(wst, w.stamp, kStampSchur, bid * kSchurWaves + wv, !HPP_ONLY && lane == 0);       // per wave, of one launch
 }
 
 #ifndef MOVBA_SCHUR_MINWAVES
@@ -984,9 +950,6 @@ __device__ __forceinline__ void finalize_body(const DevWindow &w, int bid, int n
         const double zc = Rz[6] * Xf[0] + Rz[7] * Xf[1] + Rz[8] * Xf[2] + Rz[11];
         bad = (chi2 > w.chi2_gate) || !(zc > 0.0);
         const int e = w.perm ? w.perm[g] : g;          // null: the caller's edges were already grouped by map point
-#ifdef MOVBA_CLOCK_STAMP
-        if (e >= 32768)
-#endif
         w.out_chi2[e] = chi2;
         w.out_outlier[e] = (uint8_t)bad;
     }

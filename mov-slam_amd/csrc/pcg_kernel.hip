@@ -36,17 +36,6 @@
 
 namespace movba {
 
-#ifdef MOVBA_CLOCK_STAMP
-#define SEG_STAMP(k) do { unsigned long long _t; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(_t) :: "memory"); seg[k] += _t - seg_last; seg_last = _t; } while (0)
-#else
-#define SEG_STAMP(k) do { } while (0)
-#endif
-#ifdef MOVBA_CLOCK_STAMP
-#define SETUP_STAMP(k) do { const unsigned long long _t = __builtin_amdgcn_s_memtime(); if (tid == 0) c->dbg_seg2[k] += _t - setup_last; setup_last = _t; } while (0)
-#else
-#define SETUP_STAMP(k) do { } while (0)
-#endif
-
 // wave-uniform scalars of the CG recurrences: moved to scalar registers (two VGPRs less per value) or left where they are
 #ifdef MOVBA_PCG_NO_UNIFORM
 #define PCG_UNI(x) (x)
@@ -106,10 +95,8 @@ __device__ __forceinline__ void pcg_rows_body(const DevWindow &w, const PcgParam
     const int ctrial = fresh ? trial : trial - 1;         // the trial whose coarse matrix preconditions this solve
     int cur = 0;
     double lambda = 0.0;
-#ifdef MOVBA_CLOCK_STAMP
-    const unsigned long long stamp_c0 = __builtin_amdgcn_s_memtime(), stamp_t0 = __builtin_amdgcn_s_memrealtime();
-    unsigned long long setup_last = stamp_c0;
-#endif
+    STAMP_SPAN(run);                    // the solving workgroup's launch in shader cycles and, beside them, in 10 ns ticks
+    STAMP_SEGMENTS(setup, 8); STAMP_SEG_START(setup);
     const double *part = w.part;
     if (!solver) {
         // the coarse-level workgroup, and a solver that builds its coarse level first, read every partial of the schur pass
@@ -169,7 +156,7 @@ __device__ __forceinline__ void pcg_rows_body(const DevWindow &w, const PcgParam
             for (int q = 0; q < 36; ++q) Bo[k][q] = w.img_b[(size_t)(36 * k + q) * kT + tid];
     }
     if (solver && done_w) return;
-    SETUP_STAMP(6);
+    STAMP_SEG(setup, 6);
     const int npad = (n + 1) & ~1;
     const int nrowent_all = rp_nf;
 
@@ -307,7 +294,7 @@ __device__ __forceinline__ void pcg_rows_body(const DevWindow &w, const PcgParam
 #pragma unroll
         for (int q = 0; q < 6; ++q) mi[q] = d6[q];
     }
-    SETUP_STAMP(7);
+    STAMP_SEG(setup, 7);
     // (coarse level: usable when the previous trial's launch left a valid inverse - never for the first trial; on its way into
     //  LDS since the top of the kernel)
     // ---- block-Jacobi preconditioner: S_ii^-1 by the block's six owner lanes, each holding a row: in-place Gauss-Jordan, the
@@ -362,7 +349,7 @@ __device__ __forceinline__ void pcg_rows_body(const DevWindow &w, const PcgParam
         if (ln == 0) reinterpret_cast<int *>(red1)[wv] = wbad;
     }
     const bool coarse = pp.use_coarse && ctrial >= 0 && aci_tag == ctrial;
-    SETUP_STAMP(0);
+    STAMP_SEG(setup, 0);
     // (a keyframe's diagonal block is read by a lane of the wave that owns its rows: no workgroup barrier between the two)
     wave_lds_sync0();
 
@@ -410,7 +397,7 @@ __device__ __forceinline__ void pcg_rows_body(const DevWindow &w, const PcgParam
                 for (int q = 0; q < 6; ++q) Bo[k][a * 6 + q] = mine ? (tr ? raw[q * 6 + a] : raw[a * 6 + q]) : Bo[k][a * 6 + q];
         }
     }
-    SETUP_STAMP(1);
+    STAMP_SEG(setup, 1);
 
     double x_r = 0.0, z_r = 0.0;
     // z = Minv r: a block's six rows sit in one wave, so its residuals are exchanged through LDS
@@ -545,13 +532,11 @@ __device__ __forceinline__ void pcg_rows_body(const DevWindow &w, const PcgParam
     // there were four of them in a row on the chain of every iteration; this way the branch finds its condition long computed.
     int stop = 0;
 
-#ifdef MOVBA_CLOCK_STAMP
-    unsigned long long seg[8] = { 0, 0, 0, 0, 0, 0, 0, 0 }, seg_last = __builtin_amdgcn_s_memtime();
-#endif
+    STAMP_SEGMENTS(seg, 8); STAMP_SEG_START(seg);
     if (!fail) {
         for (iters = 1; iters <= pp.max_iters; ++iters) {
             if (stop) break;
-            SEG_STAMP(7);
+            STAMP_SEG(seg, 7);
             // ---- x += alpha p, r -= alpha s, z = Minv r (wave-local) ----
             x_r += alpha * p_r;
             r_r -= alpha * s_r;
@@ -571,9 +556,9 @@ __device__ __forceinline__ void pcg_rows_body(const DevWindow &w, const PcgParam
             //  launch against 62.2 - 62.7, same box)
             z_r = precond(r_r);
             if (owner) p_lds[row] = z_r;                      // the vector the mat-vec multiplies
-            SEG_STAMP(0);
+            STAMP_SEG(seg, 0);
             __syncthreads();                                  // (A) z visible
-            SEG_STAMP(1);
+            STAMP_SEG(seg, 1);
             // ---- y = B0 z_c0 + B1 z_c1 for this lane's pair, parked in the wave's strip of ypart ----
             // (branch-free: a lane without a pair multiplies zeros and writes the dummy strip)
             {
@@ -613,7 +598,7 @@ __device__ __forceinline__ void pcg_rows_body(const DevWindow &w, const PcgParam
                 double2 *yo = reinterpret_cast<double2 *>(ypart + pq * 6);
                 yo[0] = make_double2(y[0], y[1]); yo[1] = make_double2(y[2], y[3]); yo[2] = make_double2(y[4], y[5]);
             }
-            SEG_STAMP(2);
+            STAMP_SEG(seg, 2);
             wave_lds_sync();
             // owner: add up its row's pair sums in list order; loads issued together, adds in order
             double w_r = 0.0;
@@ -639,7 +624,7 @@ __device__ __forceinline__ void pcg_rows_body(const DevWindow &w, const PcgParam
                     w_r += (((v[0] + v[1]) + (v[2] + v[3])) + ((v[4] + v[5]) + (v[6] + v[7]))) + (v[8] + v[9]);
                 }
             }
-            SEG_STAMP(3);
+            STAMP_SEG(seg, 3);
             double rv10[10];
             if (coarse) restrict_issue(w_r, rv10);            // P^T w of this wave's aggregate, published with the dot-product partials
             {
@@ -648,9 +633,9 @@ __device__ __forceinline__ void pcg_rows_body(const DevWindow &w, const PcgParam
                 if (ln == 0) *reinterpret_cast<double2 *>(red0 + 2 * wv) = make_double2(g, d);      // (red0 / red1: one run of 2 kNW doubles)
             }
             if (coarse) restrict_finish(rv10);
-            SEG_STAMP(4);
+            STAMP_SEG(seg, 4);
             __syncthreads();                                  // (B) r.z, w.z and P^T w visible; all reads of z done
-            SEG_STAMP(5);
+            STAMP_SEG(seg, 5);
             // the eight waves' (r.z, w.z): lane k < 8 reads wave k's pair, three DPP steps add them in the fixed tree
             // ((0 + 1) + (2 + 3)) + ((4 + 5) + (6 + 7)) - ONE 16-byte LDS read per lane and six adds where every lane used to read
             // all sixteen values and add them up itself; requested ahead of the coarse product's reads (LDS answers in order: the
@@ -702,7 +687,7 @@ __device__ __forceinline__ void pcg_rows_body(const DevWindow &w, const PcgParam
                 u_reg = yc + beta * u_reg;
                 wave_lds_sync();                              // u_c is read by lanes 0-11 at the top of the next iteration
             }
-            SEG_STAMP(6);
+            STAMP_SEG(seg, 6);
         }
     }
     if (stop) { iters = stop == 3 ? 0 : iters - 1; fail = stop == 1; }      // (the loop counted one more before it looked)
@@ -753,20 +738,14 @@ __device__ __forceinline__ void pcg_rows_body(const DevWindow &w, const PcgParam
         const int h = i == tid ? h0 : w.hidx[i];
         store_trial_pose(S1.pose, S1.Rt, i, T, h, true, p_lds);
     }
-#ifdef MOVBA_CLOCK_STAMP
-    if (ln == 0) for (int k = 0; k < 8; ++k) c->dbg_wseg[wv][k] += seg[k];
-#endif
+    STAMP_SEG_FLUSH(seg, 8, w.stamp, kSegWave + 8 * wv, ln == 0);
     if (tid == 0) {
         w.scale_part[w.n_pt_blocks] = scs;
         c->pcg_fail = 0;
         c->pcg_last_iters = iters;
         c->pcg_total_iters += iters;
-#ifdef MOVBA_CLOCK_STAMP
-        c->dbg_cycles += __builtin_amdgcn_s_memtime() - stamp_c0;
-        c->dbg_ticks += __builtin_amdgcn_s_memrealtime() - stamp_t0;
-        for (int k = 0; k < 8; ++k) c->dbg_seg[k] += seg[k];
-        (void)setup_last;
-#endif
+        STAMP_SPAN_END(run, w.stamp, kSegCycles, kSegTicks, true);
+        STAMP_SEG_FLUSH(seg, 8, w.stamp, kSegIter, true); STAMP_SEG_FLUSH(setup, 8, w.stamp, kSegPhase, true);
     }
 }
 

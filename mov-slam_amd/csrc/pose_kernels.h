@@ -4,6 +4,8 @@
 
 #include <cstdint>
 
+#include "clock_stamp.h"
+
 namespace movba {
 
 struct PoseDev {
@@ -22,6 +24,9 @@ struct PoseDev {
                             // stopping rule admitted | LO refit kept (0 / 1) | inliers of the LM's start pose
     const int32_t *samples; // n_hyp x 3
     double *cand;           // device scratch for the candidate poses and scores (pose_ransac_bytes); unused when the stage runs staged in k_pose_opt
+#ifdef MOVBA_CLOCK_STAMP
+    StampBuf stamp;         // diagnostic build only, behind everything the product build has (clock_stamp.h)
+#endif
 };
 
 // staged: inputs and outputs are device views of pinned host memory, the kernel keeps the matches in LDS

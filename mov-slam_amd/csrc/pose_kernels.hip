@@ -425,14 +425,7 @@ __device__ __forceinline__ void pose_opt_body(const PoseDev &p)
     };
 
     int n_bad = 0, n_lm = 0;
-#ifdef MOVBA_CLOCK_STAMP
-    unsigned long long pseg[4] = { 0, 0, 0, 0 }, plast = 0;
-#define POSE_STAMP0() do { asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(plast) :: "memory"); } while (0)
-#define POSE_STAMP(k) do { unsigned long long t_; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_) :: "memory"); pseg[k] += t_ - plast; plast = t_; } while (0)
-#else
-#define POSE_STAMP0() do { } while (0)
-#define POSE_STAMP(k) do { } while (0)
-#endif
+    STAMP_SEGMENTS(pseg, 4);
     // the LM iterations of one round over the active matches (level1 == 0), from and into `pose`
     auto lm_round = [&](bool robust, int its) {
         double cnt[1] = { 0.0 };
@@ -442,7 +435,7 @@ __device__ __forceinline__ void pose_opt_body(const PoseDev &p)
         double lambda = 0.0, ni = 2.0;
         for (int it = 0; it < its && ok; ++it) {
             ++n_lm;
-            POSE_STAMP0();
+            STAMP_SEG_START(pseg);
             // computeActiveErrors + buildSystem in one pass
             double R[12];
             q2R(pose, R);
@@ -495,9 +488,9 @@ __device__ __forceinline__ void pose_opt_body(const PoseDev &p)
                 acc[27] += rho0;
               }
             }
-            POSE_STAMP(0);
+            STAMP_SEG(pseg, 0);
             reduce_all<kW>(acc, lds, flip);
-            POSE_STAMP(1);
+            STAMP_SEG(pseg, 1);
             double F0 = acc[27];
             if (it == 0) {
                 double md = 0.0;
@@ -513,9 +506,9 @@ __device__ __forceinline__ void pose_opt_body(const PoseDev &p)
                 for (int k = 0; k < 7; ++k) bk[k] = pose[k];
                 const bool ok2 = solve6(acc, lambda, acc + 21, x);
                 if (ok2) oplus(x, bk, pose);
-                POSE_STAMP(2);
+                STAMP_SEG(pseg, 2);
                 double F1 = cost(pose, robust);
-                POSE_STAMP(3);
+                STAMP_SEG(pseg, 3);
                 if (!ok2) F1 = DBL_MAX;
                 double scale = 1e-3;
                 if (ok2) {
@@ -627,9 +620,7 @@ __device__ __forceinline__ void pose_opt_body(const PoseDev &p)
         for (int k = 0; k < 7; ++k) p.pose_out[k] = pose[k];
         p.pose_out[7] = (double)(p.n - n_bad);
         p.pose_out[16] = (double)n_lm;
-#ifdef MOVBA_CLOCK_STAMP
-        for (int k = 0; k < 4; ++k) p.pose_out[20 + k] = (double)pseg[k];
-#endif
+        STAMP_SEG_FLUSH(pseg, 4, p.stamp, 0, true);
     }
 }
 

@@ -45,7 +45,7 @@ void carve_inputs(Carver &c, FrameLayout &L)
 }
 void carve_results(Carver &c, FrameLayout &L)
 {
-    L.o_chi = c.take<double>(L.n); L.o_pose = c.take<double>(24); L.o_lvl = c.take<uint8_t>(L.n);
+    L.o_chi = c.take<double>(L.n); L.o_pose = c.take<double>(20); L.o_lvl = c.take<uint8_t>(L.n);
 }
 
 void pack_inputs(char *sg, const FrameLayout &L, const movba_pose_desc &d)
@@ -78,7 +78,7 @@ void clear_counts(movba_pose_result &r)
     r.n_inliers = 0; r.ransac_inliers = 0; r.lm_iters = 0; r.ransac_samples_used = 0; r.lo_accepted = 0; r.lo_inliers = 0; r.pad_q = 0;
 }
 
-// a solved frame's result out of the staging buffer: the 24-double record the LM kernel leaves, the flags and the errors
+// a solved frame's result out of the staging buffer: the 20-double record the LM kernel leaves, the flags and the errors
 void read_result(const char *sg, const FrameLayout &L, const movba_pose_desc &d, movba_pose_result &r)
 {
     const double *po = reinterpret_cast<const double *>(sg + L.o_pose);
@@ -143,6 +143,7 @@ int movba_pose_opt(movba_handle *h, const movba_pose_desc *d, movba_pose_result 
     pack_inputs(sg, L, *d);
     if (need_arena) HIP_TRY(hipMemcpyAsync(ar, sg, h2d, hipMemcpyHostToDevice, h->stream));
     PoseDev p = pose_dev(*d, L, need_arena ? ar : h->stage_dev, staged ? h->stage_dev : ar, need_arena ? ar + L.o_cand : nullptr);
+    STAMP_HOST(rc = stamp_pose(h, p); if (rc) return rc);
     if (grid_hyp) {
         HIP_TRY(launch_pose_hyp(p, h->stream));
         p.hyp_done = 1;
@@ -151,11 +152,7 @@ int movba_pose_opt(movba_handle *h, const movba_pose_desc *d, movba_pose_result 
     if (!staged) HIP_TRY(hipMemcpyAsync(sg + L.o_chi, ar + L.o_chi, d2h_end - L.o_chi, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
     read_result(sg, L, *d, *res);
-#ifdef MOVBA_CLOCK_STAMP
-    const double *po = reinterpret_cast<const double *>(sg + L.o_pose);
-    std::fprintf(stderr, "libmovba[stamp]: k_pose_opt, cycles per LM iteration (%d): system pass %.0f, reduction of 28 %.0f, solve + update %.0f, cost pass + reduction %.0f\n",
-                 res->lm_iters, po[20] / res->lm_iters, po[21] / res->lm_iters, po[22] / res->lm_iters, po[23] / res->lm_iters);
-#endif
+    STAMP_HOST(stamp_report_pose(h, res->lm_iters));
     return MOVBA_OK;
 }
 

@@ -1261,6 +1261,7 @@ int movba_lba_upload(movba_handle *h, const movba_lba_desc *d)
     }
     // (movba_lba_marginals: fixed keyframes get zero blocks, free ones outside the system NaN - the hessian index alone does not
     //  tell them apart)
+    STAMP_HOST(if (rc == MOVBA_OK) rc = stamp_window(h));
     if (rc == MOVBA_OK) h->pose_fixed.assign(d->pose_fixed, d->pose_fixed + (d->pose_fixed ? d->n_poses : 0));
     return rc;
 }

@@ -633,6 +633,21 @@ class Solver:
         if rc != OK:
             raise MovbaError(f"movba_test_hook({name}): {status_string(rc)}")
 
+    def stamp_records(self, cls: int):
+        """movba_stamp_records (clock-stamp build only, -DMOVBA_CLOCK_STAMP; not in include/movba.h): the records the last run left,
+        (n, 8) uint64; cls 0: back-substitution pass per workgroup, 1: k_schur per wave, 2: the segment slots"""
+        if not hasattr(self._L, "movba_stamp_records"):
+            raise MovbaError("movba_stamp_records exists in the clock-stamp build only (MOVBA_LIB)")
+        f = self._L.movba_stamp_records
+        f.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
+        n = f(self._h, cls, None, 0)
+        if n < 0:
+            raise MovbaError(f"movba_stamp_records: {status_string(n)}")
+        a = np.zeros((n, 8), np.uint64)
+        if f(self._h, cls, a.ctypes.data, n) != n:
+            raise MovbaError("movba_stamp_records: the record count changed between two calls")
+        return a
+
     def close(self):
         if self._h:
             self._L.movba_destroy(self._h)

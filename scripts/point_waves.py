@@ -1,4 +1,4 @@
-"""Stamp build only (-DMOVBA_CLOCK_STAMP): per-workgroup phase stamps of one back-substitution pass (k_point<true>), smuggled out through chi2."""
+"""Stamp build only (-DMOVBA_CLOCK_STAMP): per-workgroup phase stamps of one back-substitution pass (k_point<true>), read through movba_stamp_records."""
 import sys, os
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "mov-slam_amd"))
@@ -6,7 +6,7 @@ import numpy as np
 from movba import synth, capi
 w = synth.cfg(sys.argv[1] if len(sys.argv) > 1 else "cfg3")
 s = capi.Solver(); s.upload(w); s.run(); s.run(); r = s.download()
-st = r["chi2"][20000:32768].view(np.uint64).reshape(-1, 8).astype(np.int64)
+st = s.stamp_records(0).astype(np.int64)
 blk = st[st[:, 7] == 1]; dec = st[st[:, 7] == 2]
 t0 = blk[:, 0].min()
 T = (blk[:, :6] - t0) * 0.01

@@ -1,4 +1,4 @@
-"""Stamp build only (-DMOVBA_CLOCK_STAMP): per-wave phase stamps of one k_schur launch, smuggled out through chi2."""
+"""Stamp build only (-DMOVBA_CLOCK_STAMP): per-wave phase stamps of one k_schur launch, read through movba_stamp_records."""
 import sys, os
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "mov-slam_amd"))
@@ -6,7 +6,7 @@ import numpy as np
 from movba import synth, capi
 w = synth.cfg("cfg3")
 s = capi.Solver(); s.upload(w); s.run(); s.run(); r = s.download()
-st = r["chi2"][:20000].view(np.uint64).reshape(-1, 8).astype(np.int64)
+st = s.stamp_records(1).astype(np.int64)
 st = st[st[:, 7] == 1]
 t0 = st[:, 0].min()
 T = (st[:, :5] - t0) * 0.01
