@@ -342,7 +342,7 @@ int  movba_pose_ransac_samples(int32_t n, int32_t n_hyp, uint32_t seed, int32_t 
  * match of every pair is triangulated (or un-projected from a stereo observation) and taken through the reference's gates
  * in the reference's order.  Choosing the neighbours (the baseline test at :268-287 with ComputeSceneMedianDepth included:
  * a neighbour the reference skips is simply not passed), matching (MOVMatcher::SearchForTriangulation, :292) and the MapPoint
- * bookkeeping (:483-494) stay with the caller.  Pairs are independent: one call serves one keyframe against its 30
+ * bookkeeping (:483-494) stay with the caller (the matching is movba_track_match, whose output has this call's layout).  Pairs are independent: one call serves one keyframe against its 30
  * neighbours, or the keyframes of many sessions. */
 typedef struct {
     /* views */
@@ -648,7 +648,7 @@ int  movba_init_map(movba_handle *h, const movba_init_map_desc *descs, movba_ini
  * head of MOVMatcher::Fuse (MOVMatcher.h:207-245, from LocalMapping::SearchInNeighbors, LocalMapping.cc:558, :586) and
  * KeyFrame::ComputeSceneMedianDepth (KeyFrame.cc:757-791), which feeds the baseline test in front of triangulation
  * (LocalMapping.cc:268-287).  A view is one frame or keyframe with one list of map points in one mode; a keyframe that needs
- * two lists appears as two views.  The mnLastFrameSeen and isBad filters, IncreaseVisible, the track-id lookup, Replace and
+ * two lists appears as two views.  The mnLastFrameSeen and isBad filters, IncreaseVisible, the track-id lookup (movba_track_match), Replace and
  * AddObservation, the far-points test on track_depth and the division baseline / median_depth stay with the caller. */
 #define MOVBA_VIEW_FRUSTUM 0   /* Frame.cc:464-518, the monocular branch (this fork's frames have Nleft == -1)          */
 #define MOVBA_VIEW_FUSE    1   /* MOVMatcher.h:207-245                                                                  */
@@ -906,6 +906,85 @@ typedef struct {
  * with an uploaded or solved window, waiting for the window's arrays before it reuses the staging buffer: the window, its
  * results, its marginals and later runs stay as they were. */
 int  movba_covisibility(movba_handle *h, const movba_covis_desc *desc, movba_covis_result *res);
+
+/* The track-id joins of MOVMatcher for many views per call.  In this fork every matcher function is a join on
+ * VideoFeature::trackId: SearchForTriangulation (MOVMatcher.h:139-168) is a double loop over the slots of two keyframes, run once
+ * per neighbour of a new keyframe; both SearchByVideoFeature (:35-103), SearchForInitialization (:105-137) and the keypoint loop
+ * at the tail of Fuse (:249-273) look ids up in a view.  This call is what stands between the other calls: movba_covisibility
+ * picks the neighbours, this call joins them, movba_triangulate takes the matches; movba_view_points followed by this call is
+ * SearchByVideoFeature and Fuse.  Everything is integer: the result is exact. */
+#define MOVBA_TM_TRIANGULATION 0   /* SearchForTriangulation, MOVMatcher.h:139-168                                          */
+#define MOVBA_TM_LOOKUP        1   /* the mvVFMap lookups: both SearchByVideoFeature (:35-103), SearchForInitialization
+                                      (:105-137), and the keypoint loop of Fuse (:249-273)                                  */
+#define MOVBA_MAX_TRACK_SLOTS   16384   /* slots of one view */
+#define MOVBA_MAX_TRACK_QUERIES 4096
+
+typedef struct {
+    int32_t n_views, n_queries;
+    const int32_t *view_ptr;        /* n_views + 1, ascending, [0] = 0: the slots of view v are [view_ptr[v], view_ptr[v + 1]);
+                                       n_slots = view_ptr[n_views]                                                          */
+    const int32_t *slot_track;      /* n_slots: mvVF[j].trackId in slot order; any int32 is an id (0, negatives, INT32_MIN) */
+    const uint8_t *slot_taken;      /* n_slots or NULL (no slot is taken): != 0 where GetMapPointMatches()[j] != NULL       */
+    /* per-slot payload, gathered for the TRIANGULATION matches; each may be NULL */
+    const double  *slot_obs;        /* n_slots x 2: the keypoint (mvKeysUn[j].pt)                                           */
+    const double  *slot_ur;         /* n_slots: mvuRight[j]                                                                 */
+    const double  *slot_depth;      /* n_slots: mvDepth[j]                                                                  */
+    /* queries */
+    const int32_t *query_mode;      /* n_queries: MOVBA_TM_*                                                                */
+    const int32_t *query_view;      /* n_queries x 2.  TRIANGULATION: (view 1 = the current keyframe, view 2 = the neighbour),
+                                       which may be equal; LOOKUP: (-1, the view searched)                                  */
+    const int32_t *query_ptr;       /* n_queries + 1, ascending, [0] = 0; n_items = query_ptr[n_queries]                    */
+    const int32_t *item_track;      /* n_items: the ids a LOOKUP query looks up; a TRIANGULATION query has an empty range   */
+} movba_track_desc;     /* 88 bytes */
+
+/* match_cap = the sum over the TRIANGULATION queries of the slot count of view 1: what the caller allocates for. */
+typedef struct {
+    int32_t *pair_ptr;              /* n_queries + 1: dense ascending prefix of the queries' match counts (LOOKUP queries
+                                       contribute 0): the layout movba_tri_desc::pair_ptr takes                             */
+    int32_t *match_slot1;           /* match_cap: slot in view 1, local to the view (vMatchedIndices), dense in query order,
+                                       ascending within a query; -1 behind pair_ptr[n_queries]                              */
+    int32_t *match_slot2;           /* match_cap: slot in view 2                                                            */
+    /* the payload of the matched slots, in the layout of movba_tri_desc::obs1 .. depth2; each NULL or match_cap entries (x 2
+       for obs), NaN behind the last match.  An output whose source array is NULL must be NULL.                             */
+    double  *obs1, *obs2;
+    double  *ur1, *ur2;
+    double  *depth1, *depth2;
+    int32_t *item_slot;             /* n_items: per item of a LOOKUP query the slot found, local to the view, or -1         */
+    int32_t *n_found;               /* n_queries: items found (the nmatches the lookups return); 0 for TRIANGULATION        */
+    int32_t  n_matches;             /* pair_ptr[n_queries]                                                                  */
+    int32_t  status;
+} movba_track_result;   /* 96 bytes */
+
+/* Restated as written, query by query:
+ *   TRIANGULATION  for every slot i of view 1 in ascending order with taken[i] == 0: the lowest slot j of view 2 with
+ *              taken[j] == 0 and the id of i; if there is one, (i, j) is a match (the inner loop's `break`, :150-163).  Nothing
+ *              makes matches unique: two slots of view 1 that carry one id both match the same j, as in the reference.  The
+ *              matches of a query stand in ascending i.  The reference returns an uninitialised nmatches; here the count of a
+ *              query is vMatchedPairs.size(), pair_ptr[q + 1] - pair_ptr[q].
+ *   LOOKUP     for every item the lowest slot of the view that carries the id, or -1; slot_taken is not looked at.  That is
+ *              what std::map::insert leaves in mvVFMap when the map is filled in slot order - the first insertion wins - and
+ *              what the ascending scan with `break` of Fuse finds.  MOVExtractor.cc:249 sorts the previous frame's mvVF without
+ *              rebuilding its map: a caller who wants that stale map passes the ids in the order the map was built.
+ * What stays with the caller: applying the hits in item order (F.mvpMapPoints[slot] = pMP: a later item overwrites an earlier
+ * one on the same slot), the isBad, mbTrackInView and far-point filters (a filtered point is simply not passed), Replace and
+ * AddObservation.
+ * A query's result depends on the slots of its own views, or on its own items and the view it searches - not on the other
+ * queries, their order, or how the queries are split over calls - and two calls give the same bits: the join is integer, the
+ * payload is copied bit for bit (NaN payloads included), floating-point arithmetic does not occur.
+ * Returns MOVBA_ERR_ARG for a NULL handle, descriptor or result; a negative count; n_queries > MOVBA_MAX_TRACK_QUERIES; a view of
+ * more than MOVBA_MAX_TRACK_SLOTS slots; n_slots, n_items or match_cap above 2^28 (match_cap is at most 2^26 under the two bounds before it); view_ptr or query_ptr not ascending or not
+ * starting at 0; an unknown mode; a view index outside 0 .. n_views - 1, a LOOKUP query whose first view is not -1, a
+ * TRIANGULATION query with items; a NULL array that the counts make necessary (query_mode, query_view, query_ptr, view_ptr,
+ * pair_ptr and n_found when n_queries > 0; slot_track when n_slots > 0; item_track and item_slot when n_items > 0; match_slot1
+ * and match_slot2 when match_cap > 0); a payload output given without its source.  MOVBA_ERR_HIP as elsewhere.  Every argument
+ * is checked before anything is queued, and on a non-zero status nothing is written except `status`.  n_queries == 0 (with counts
+ * that are otherwise in range): MOVBA_OK and nothing else written, the arrays are not looked at.
+ * One packed copy to the device, two launches - k_tm_match, one workgroup per query with an open-addressing table over the
+ * searched view's slots in its LDS, which is what bounds the slots of a view, then k_tm_pack, which makes the matches dense,
+ * gathers the payload and pads the tail - and one synchronisation; result arrays that lie in movba_host_alloc memory are written
+ * by the kernels themselves.  May share a handle with an uploaded or solved window, waiting for the window's arrays before it
+ * reuses the staging buffer: the window, its results, its marginals and later runs stay as they were. */
+int  movba_track_match(movba_handle *h, const movba_track_desc *desc, movba_track_result *res);
 
 #ifdef __cplusplus
 }

@@ -168,6 +168,23 @@ class CovisResult(C.Structure):
                 ("out_weight", _i), ("status", C.c_int32), ("pad", C.c_int32)]
 
 
+class TrackDesc(C.Structure):
+    _fields_ = [("n_views", C.c_int32), ("n_queries", C.c_int32), ("view_ptr", _i), ("slot_track", _i), ("slot_taken", _u),
+                ("slot_obs", _d), ("slot_ur", _d), ("slot_depth", _d), ("query_mode", _i), ("query_view", _i), ("query_ptr", _i),
+                ("item_track", _i)]
+
+
+class TrackResult(C.Structure):
+    _fields_ = [("pair_ptr", _i), ("match_slot1", _i), ("match_slot2", _i), ("obs1", _d), ("obs2", _d), ("ur1", _d), ("ur2", _d),
+                ("depth1", _d), ("depth2", _d), ("item_slot", _i), ("n_found", _i), ("n_matches", C.c_int32), ("status", C.c_int32)]
+
+
+# movba_track_desc::query_mode (MOVBA_TM_*)
+TM_TRIANGULATION, TM_LOOKUP = 0, 1
+MAX_TRACK_SLOTS = 16384
+MAX_TRACK_QUERIES = 4096
+TRACK_INT_ARRAYS = ("pair_ptr", "match_slot1", "match_slot2", "item_slot", "n_found")
+TRACK_PAYLOAD = (("obs1", "obs"), ("obs2", "obs"), ("ur1", "ur"), ("ur2", "ur"), ("depth1", "depth"), ("depth2", "depth"))
 MAX_COVIS_VIEWS = 8192
 MAX_COVIS_QUERIES = 4096
 COVIS_ARRAYS = ("n_counted", "n_connected", "best_view", "best_weight", "out_view", "out_weight")
@@ -206,7 +223,7 @@ EXPORTS = ["movba_version", "movba_status_string", "movba_create", "movba_destro
            "movba_structure_probe", "movba_pose_opt", "movba_set_profile_mask", "movba_lba_run_batch", "movba_pose_ransac_samples",
            "movba_host_alloc", "movba_host_free", "movba_dense_plan_probe", "movba_pose_opt_batch", "movba_lba_marginals", "movba_triangulate",
            "movba_two_view", "movba_two_view_samples", "movba_two_view_lo", "movba_init_map", "movba_view_points",
-           "movba_point_normals", "movba_lba_point_normals", "movba_covisibility"]
+           "movba_point_normals", "movba_lba_point_normals", "movba_covisibility", "movba_track_match"]
 
 _libs = {False: None, True: None}
 
@@ -271,6 +288,7 @@ def lib(hooks: bool = False):
         L.movba_point_normals.argtypes = [C.c_void_p, C.POINTER(NormalsDesc), C.POINTER(NormalsResult)]
         L.movba_lba_point_normals.argtypes = [C.c_void_p, _i, _i, _d, C.c_int32, _u, _d, _d, _d]
         L.movba_covisibility.argtypes = [C.c_void_p, C.POINTER(CovisDesc), C.POINTER(CovisResult)]
+        L.movba_track_match.argtypes = [C.c_void_p, C.POINTER(TrackDesc), C.POINTER(TrackResult)]
         L.movba_host_alloc.argtypes = [C.c_size_t]
         L.movba_host_alloc.restype = C.c_void_p
         L.movba_dense_plan_probe.argtypes = [C.c_int32, C.c_int32, C.c_int32, _i, _i, C.c_int32, _i, C.c_int32]
@@ -595,6 +613,64 @@ def covis_result(n_queries, max_out, alloc=np.zeros):
     for key in COVIS_ARRAYS:
         if keep[key].size or key in COVIS_ARRAYS[:4]:
             setattr(r, key, _p(keep[key], _i))
+    return r, keep
+
+
+def track_desc(views, queries):
+    """views: one dict per view with track (n,) int32 ids in slot order and optionally taken (n,), obs (n, 2), ur (n,), depth (n,)
+    (an optional array is given for every view or for none); queries: (TM_TRIANGULATION, view 1, view 2) or (TM_LOOKUP, view,
+    ids) -> (movba_track_desc, the arrays it points into; keep["match_cap"]: the sum of view 1's slots over the TRIANGULATION
+    queries, what the result arrays are sized to)."""
+    tracks = [np.asarray(v["track"], np.int32).reshape(-1) for v in views]
+    keep = dict(view_ptr=np.concatenate([[0], np.cumsum([len(t) for t in tracks])]).astype(np.int32),
+                slot_track=np.ascontiguousarray(np.concatenate(tracks) if tracks else np.zeros(0), np.int32))
+    for key, field, dtype, width in (("taken", "slot_taken", np.uint8, 1), ("obs", "slot_obs", np.float64, 2), ("ur", "slot_ur", np.float64, 1),
+                                     ("depth", "slot_depth", np.float64, 1)):
+        have = [key in v and v[key] is not None for v in views]
+        if not any(have):
+            continue
+        if not all(have):
+            raise ValueError(f"track_desc: {key} is given for every view or for none")
+        parts = [np.asarray(v[key], dtype).reshape(len(t), width) for v, t in zip(views, tracks)]
+        keep[field] = np.ascontiguousarray(np.concatenate(parts), dtype)
+    modes, qviews, items, cap = [], [], [], 0
+    for q in queries:
+        modes.append(int(q[0]))
+        if q[0] == TM_LOOKUP:
+            qviews.append((-1, int(q[1])))
+            items.append(np.asarray(q[2], np.int32).reshape(-1))
+        else:
+            qviews.append((int(q[1]), int(q[2])))
+            items.append(np.zeros(0, np.int32))
+            if q[0] == TM_TRIANGULATION and 0 <= int(q[1]) < len(tracks):
+                cap += len(tracks[int(q[1])])
+    keep["query_mode"] = np.array(modes, np.int32)
+    keep["query_view"] = np.array(qviews, np.int32).reshape(len(modes), 2)
+    keep["query_ptr"] = np.concatenate([[0], np.cumsum([len(i) for i in items])]).astype(np.int32)
+    keep["item_track"] = np.ascontiguousarray(np.concatenate(items) if items else np.zeros(0), np.int32)
+    keep["match_cap"] = cap
+    d = TrackDesc()
+    d.n_views, d.n_queries = len(tracks), len(modes)
+    for key in ("view_ptr", "slot_track", "query_mode", "query_view", "query_ptr", "item_track"):
+        setattr(d, key, _p(keep[key], _i))
+    if "slot_taken" in keep:
+        d.slot_taken = _p(keep["slot_taken"], _u)
+    for key in ("slot_obs", "slot_ur", "slot_depth"):
+        if key in keep:
+            setattr(d, key, _p(keep[key], _d))
+    return d, keep
+
+
+def track_result(n_queries, n_items, match_cap, payload=(), alloc=np.zeros):
+    """-> (movba_track_result with its output arrays, the arrays it points into); payload: which of obs1 .. depth2 to gather"""
+    keep = dict(pair_ptr=alloc((n_queries + 1,), np.int32), match_slot1=alloc((match_cap,), np.int32), match_slot2=alloc((match_cap,), np.int32),
+                item_slot=alloc((n_items,), np.int32), n_found=alloc((n_queries,), np.int32))
+    r = TrackResult()
+    for key in TRACK_INT_ARRAYS:
+        setattr(r, key, _p(keep[key], _i))
+    for key in payload:
+        keep[key] = alloc((match_cap, 2) if key.startswith("obs") else (match_cap,), np.float64)
+        setattr(r, key, _p(keep[key], _d))
     return r, keep
 
 
@@ -994,6 +1070,22 @@ class Solver:
             raise MovbaError(f"movba_covisibility: {status_string(rc)}")
         out["status"] = rc
         return out
+
+    def track_match(self, views, queries, pinned=False) -> dict:
+        """movba_track_match (the track-id joins of MOVMatcher): arguments as track_desc -> dict(status, n_matches, pair_ptr, pairs =
+        dict(pair_view, pair_ptr), matches = dict(obs1, obs2, ur1, ur2, depth1, depth2: those whose source the views carry),
+        match_slot1, match_slot2 (match_cap,), item_slot (n_items,), query_ptr, n_found).  `pairs` and `matches` are what
+        Solver.triangulate takes, unchanged, when every query of the call is a TRIANGULATION query (a LOOKUP query stands in
+        pair_view with view 1 = -1).  pinned: result arrays in movba_host_alloc memory, written by the kernels themselves."""
+        d, keep = track_desc(views, queries)
+        payload = [key for key, src in TRACK_PAYLOAD if "slot_" + src in keep]
+        r, out = track_result(d.n_queries, len(keep["item_track"]), keep["match_cap"], payload, self._pinned if pinned else np.zeros)
+        rc = self._L.movba_track_match(self._h, C.byref(d), C.byref(r))
+        if rc < 0:
+            raise MovbaError(f"movba_track_match: {status_string(rc)}")
+        return dict(status=rc, n_matches=r.n_matches, pair_ptr=out["pair_ptr"], pairs=dict(pair_view=keep["query_view"], pair_ptr=out["pair_ptr"]),
+                    matches={key: out[key] for key in payload}, match_slot1=out["match_slot1"], match_slot2=out["match_slot2"],
+                    item_slot=out["item_slot"], query_ptr=keep["query_ptr"], n_found=out["n_found"])
 
     def lba_point_normals(self, ref_pose, ref_level, scale_factors, outlier=None, pinned=False) -> dict:
         """movba_lba_point_normals: the same quantities for every map point of the window of the last run, read where it lies
