@@ -118,7 +118,8 @@ typedef struct {
     int32_t direct_from;        /* n_solves at the switch to the dense direct solver (0: whole solve; > 0: the PCG gave up or
                                    the banded factorisation met a non-positive pivot on that trial), -1: never */
     int32_t n_chol_fail;        /* trials whose factorisation failed (dense solver: non-positive pivot; banded: NaN / inf in
-                                   the normal equations): rejected, as g2o rejects a trial whose Cholesky fails */
+                                   the normal equations): booked as the oracle books them, nothing moved, rejected unless the
+                                   current cost is infinite (mov-slam_amd/csrc/lm_rule.h; not g2o's own booking) */
     int32_t n_pcg_giveups;      /* 0 or 1: hand-overs of the solve to the dense direct solver - the PCG gave up (breakdown or
                                    iteration cap), or the banded factorisation met a finite non-positive pivot (the name is
                                    from when only the PCG could hand over)                                      */

@@ -13,6 +13,7 @@
 
 #include "device_math.h"
 #include "init_map.h"
+#include "lm_rule.h"
 #include "movba.h"
 
 namespace movba {
@@ -102,11 +103,11 @@ __global__ __launch_bounds__(kImThreads) void k_init_map(ImDev d)
         reduce_all<kW>(acc, red, flip);
         double F0 = acc[27];
         if (it == 0) {
-            // computeLambdaInit: 1e-5 max |H_jj| over the pose block and the point blocks
+            // computeLambdaInit over the pose block and the point blocks
             md = block_reduce<kW, true>(md, red + 2 * kW * kRedMax);
 #pragma unroll
             for (int a = 0; a < 6; ++a) md = fmax(fabs(acc[ut6(a, a)]), md);
-            lambda = 1e-5 * md;
+            lambda = lm_lambda_init(md);
             ni = 2.0;
             cost0 = F0;
         }
@@ -153,6 +154,8 @@ __global__ __launch_bounds__(kImThreads) void k_init_map(ImDev d)
                 fs[0] += im_cost(Rt, trial + 4, cam, huber, x, d.obs1 + 2 * m, d.obs2 + 2 * m, d.sig1[m], d.sig2[m], c2);
             }
             reduce_all<kW>(fs, red, flip);
+            // (the rest of the step rule - lm_gain, lm_accept, lm_update and the two loop conditions of lm_rule.h - written out: through
+            //  the calls the kernel's registers are numbered otherwise or its instructions change, and movba_init_map measured slower)
             double F1 = fs[0], scale = 0.0;
             if (ok2) {
 #pragma unroll

@@ -23,8 +23,10 @@
 
 #include "device_math.h"
 #include "device_types.h"
+#include "edge_model.h"
 #include "handoff.h"
 #include "kernels.h"
+#include "lm_rule.h"
 
 namespace movba {
 
@@ -62,10 +64,7 @@ __device__ __forceinline__ void init_pose_body(const DevWindow &w, int bid, int 
     store_pose_rt(w.st[0].pose, w.st[0].Rt, i, q);
 }
 
-// The camera of an edge is its keyframe's (src/Optimizer.cc:664: e->pCamera = pKFi->mpCamera; :690-695: e->fx .. e->bf from
-// pKFi): one set of intrinsics for the whole window in every shipped MoV-SLAM configuration (DevWindow::fx ..), a table by
-// keyframe when the caller hands one (movba_lba_desc::cam_kf / bf_kf).  The choice is a wave-uniform branch.
-struct Cam { double fx, fy, cx, cy, bf; };
+// The camera of an edge (Cam, edge_model.h): the window's one, or row ip of a table by keyframe; the choice is a wave-uniform branch.
 // PERKF = false: the window's one camera, straight from the kernel's scalar arguments (the instantiations every shipped
 // configuration runs: carried as a runtime choice the table's values took vector registers in k_schur, which has none to
 // spare - 17 -> 22 us per launch at cfg3); PERKF = true: row ip of DevWindow::kcam
@@ -146,36 +145,36 @@ __device__ __forceinline__ void decide_body(const DevWindow &w, int cur)
     scale = wave_sum_dpp(scale);
     if (lane != 0) return;
     scale += scale_pose;
-    // g2o on a failed solve: tempChi = DBL_MAX (std::numeric_limits<double>::max(): FINITE), scale = 1e-3, nothing updated.  With a
-    // finite current cost rho is hugely negative and the trial is rejected; with an infinite one (a point on a keyframe's z = 0
-    // plane) rho = +inf and the trial counts as ACCEPTED - of a state that has not moved, whose cost the next iteration's
-    // computeActiveErrors() finds again: F1_eval, what this pass has just summed over the unmoved trial state.
+    // The step rule and the booking of a failed solve: lm_rule.h.  Where such a trial counts as accepted (F0 = inf), the state
+    // has not moved and the next iteration's computeActiveErrors() finds its cost again: F1_eval, what this pass has just summed
+    // over the unmoved trial state.
     const double F1_eval = F1;
-    if (pcg_fail) { F1 = DBL_MAX; scale = 0.0; }
-    scale += 1e-3;
-    const double rho = (F0 - F1) / scale;
+    const LmGain gain = lm_gain(F0, F1, scale, !pcg_fail);
+    F1 = gain.F1;
+    const double rho = gain.rho;
     if (tr < kMaxTrace) {
         c->tr_lambda[tr] = lambda0; c->tr_f0[tr] = F0; c->tr_f1[tr] = F1; c->tr_rho[tr] = rho;
         c->tr_pcg[tr] = pcg_iters;
     }
     bool lambda_ok = true;
     int accepted = 0;
+    // (the three conditions below are lm_accept, lm_more_trials and lm_terminate of lm_rule.h written out: through the calls the
+    //  ten back-substitution kernels change - instruction count for the first two, the operands of one s_and_b64 for the third -
+    //  and this wave is on every trial's critical path)
+    double lam = lambda0, nu = nu0;
     if (rho > 0.0 && isfinite(F1)) {
-        const double t = 2.0 * rho - 1.0;
-        double alpha = 1.0 - t * t * t;                // (pow(tmp, 3) in g2o: a library call of ~100 instructions here)
-        alpha = fmin(alpha, 2.0 / 3.0);
-        c->lambda = lambda0 * fmax(1.0 / 3.0, alpha);
-        c->nu = 2.0;
+        lm_update(true, rho, lam, nu);
+        c->lambda = lam;
+        c->nu = nu;
         c->F0 = pcg_fail ? F1_eval : F1;
         c->cur = cur ^ 1;                    // discardTop(): the trial state becomes current
         c->last_rejected = 0;
         accepted = 1;
     } else {
-        const double lam = lambda0 * nu0;
+        lambda_ok = lm_update(false, rho, lam, nu);
         c->lambda = lam;
-        c->nu = nu0 * 2.0;
+        c->nu = nu;
         c->last_rejected = 1;                // pop(): keep the current state
-        lambda_ok = isfinite(lam);
     }
     if (tr < kMaxTrace) { c->tr_accept[tr] = accepted; c->n_trace = tr + 1; }
     const int nsolves = nsolves0 + 1, qmax = qmax0 + 1;
@@ -341,19 +340,15 @@ __device__ __forceinline__ void point_body(const DevWindow &w, int bid)
             const int h = phidx[ip];
             if (h < 0) return;
             const double *R = pR0 + 12 * ip;
-            const double x = R[0] * X[0] + R[1] * X[1] + R[2] * X[2] + R[9];
-            const double y = R[3] * X[0] + R[4] * X[1] + R[5] * X[2] + R[10];
-            const double z = R[6] * X[0] + R[7] * X[1] + R[8] * X[2] + R[11];
-            // (one reciprocal per edge and multiplications: an fp64 division is a ~25-instruction sequence, and the projection
-            //  and its Jacobian would take six of them)
+            double x, y, z;
+            cam_point(R, X, x, y, z);
             const Cam cm = cam_of<PERKF>(w, ip);
-            const double iz = fast_rcp_zero_safe(z), u = cm.fx * x * iz, v = cm.fy * y * iz;
-            const double e0 = ob.x - (u + cm.cx);
-            const double e1 = ob.y - (v + cm.cy);
-            double chi2 = e0 * (om * e0) + e1 * (om * e1);
-            if (STEREO && ur >= 0.0) { const double e2 = ur - (u + cm.cx - cm.bf * iz); chi2 += e2 * (om * e2); }
-            double rho1 = 1.0;
-            if (w.huber_delta > 0.0 && !(chi2 <= dsq0)) rho1 = w.huber_delta * rsqrt(chi2);
+            const double iz = fast_rcp_zero_safe(z);
+            double u, v, e0, e1;
+            double chi2 = edge_res_rcp(cm, x, y, iz, &ob.x, om, u, v, e0, e1);
+            if (STEREO && ur >= 0.0) edge_res_rcp_stereo(cm, u, iz, ur, om, chi2);
+            double rho0, rho1;
+            huber_rs(chi2, w.huber_delta, dsq0, rho0, rho1);       // (the weight only)
             const double wg = rho1 * om;
             const double a00 = -(cm.fx * iz), a02 = u * iz;
             const double a11 = -(cm.fy * iz), a12 = v * iz;
@@ -394,10 +389,9 @@ __device__ __forceinline__ void point_body(const DevWindow &w, int bid)
             const double x1 = D[1] * c0 + D[3] * c1 + D[4] * c2;
             const double x2 = D[2] * c0 + D[4] * c1 + D[5] * c2;
             // A reduced solve that failed (Ctrl::pcg_fail: a Cholesky factorisation that met a non-positive pivot, NaN in the
-            // normal equations) moves NOTHING: g2o's solver returns false before any vertex is updated
-            // (OptimizationAlgorithmLevenberg::solve: `ok2 = _solver->solve(); if (ok2) update`), so the trial state is the current
-            // state, evaluated once more below - which is what the next iteration's fresh cost is taken from when the decision
-            // counts such a trial as accepted (decide_body).
+            // normal equations) moves NOTHING, as in the oracle (lm_rule.h: g2o itself applies the stale increment), so the trial
+            // state is the current state, evaluated once more below - which is what the next iteration's fresh cost is taken
+            // from when the decision counts such a trial as accepted (decide_body).
             if (!c->pcg_fail) {
                 X[0] += x0; X[1] += x1; X[2] += x2;
                 if (sub == 0) scale = x0 * (lambda * x0 + b0) + x1 * (lambda * x1 + b1) + x2 * (lambda * x2 + b2);
@@ -411,28 +405,20 @@ __device__ __forceinline__ void point_body(const DevWindow &w, int bid)
     const double dsqr = w.huber_delta * w.huber_delta;
     auto eval_edge = [&](int g, int ip, int sl, const double2 &ob, double om, double ur) {
         const double *R = pRt + 12 * ip;
-        const double x = R[0] * X[0] + R[1] * X[1] + R[2] * X[2] + R[9];
-        const double y = R[3] * X[0] + R[4] * X[1] + R[5] * X[2] + R[10];
-        const double z = R[6] * X[0] + R[7] * X[1] + R[8] * X[2] + R[11];
+        double x, y, z;
+        cam_point(R, X, x, y, z);
         const Cam cm = cam_of<PERKF>(w, ip);
-        const double iz = fast_rcp_zero_safe(z), u = cm.fx * x * iz, v = cm.fy * y * iz;      // (one reciprocal per edge: see back_edge)
-        const double e0 = ob.x - (u + cm.cx);
-        const double e1 = ob.y - (v + cm.cy);
-        double chi2 = e0 * (om * e0) + e1 * (om * e1);
+        const double iz = fast_rcp_zero_safe(z);
+        double u, v, e0, e1;
+        double chi2 = edge_res_rcp(cm, x, y, iz, &ob.x, om, u, v, e0, e1);
         bool st = false;
         double e2 = 0.0;
         if (STEREO) {
             st = ur >= 0.0;
-            if (st) { e2 = ur - (u + cm.cx - cm.bf * iz); chi2 += e2 * (om * e2); }
+            if (st) e2 = edge_res_rcp_stereo(cm, u, iz, ur, om, chi2);
         }
-        double rho0 = chi2, rho1 = 1.0;
-        if (w.huber_delta > 0.0 && !(chi2 <= dsqr)) {
-            // (sqrt(chi2) = chi2 / sqrt(chi2): for chi2 = inf - a point on the keyframe's z = 0 plane - the product is inf * 0;
-            //  g2o's RobustKernelHuber takes sqrt(inf) = inf there, an infinite cost, not NaN)
-            const double rs = rsqrt(chi2), sq = chi2 > DBL_MAX ? chi2 : chi2 * rs;
-            rho0 = 2.0 * sq * w.huber_delta - dsqr;
-            rho1 = w.huber_delta * rs;
-        }
+        double rho0, rho1;
+        huber_rs(chi2, w.huber_delta, dsqr, rho0, rho1);
         const double wg = rho1 * om;
         const double r0 = -wg * e0, r1 = -wg * e1;
         if (sl >= 0) {      // pose-major record for the schur pass (edges of free keyframes): (Xc, w)
@@ -544,30 +530,7 @@ __device__ __constant__ int8_t kDiagMirror[21] = {-1, 6, 12, 18, 24, 30, -1, 13,
 // and B_il Dinv_l b_l.  Wave-level shuffle reduction, one 72-double partial per item.
 // mode 1 = diagonal pairs only, Hpp only (used once to seed lambda).
 // --------------------------------------------------------------------------------
-// Jacobian rows of one edge from its cached camera-frame point: P = J_point rows (-Jpi R), C = J_pose rows
-// (-Jpi [ -[Xc]x | I ]).  NR = 2: monocular edge (src/OptimizableTypes.cpp:158-180); NR = 3 adds the stereo row of
-// g2o::EdgeStereoSE3ProjectXYZ (built at src/Optimizer.cc:673-705), zeroed for the monocular edges of a mixed window.
-// (A division-free variant on normalised records (x / z, y / z, 1 / z) with the structural zeros of C skipped was 20 %
-//  SLOWER, solo and batched: the kernel then needs all 256 registers and the compiler schedules its gathers worse.)
-template <int NR>
-__device__ __forceinline__ void edge_rows(const Cam &cm, double x, double y, double z, const double R[9], bool stereo,
-                                          double (&P)[NR][3], double (&C)[NR][6])
-{
-    const double iz = fast_rcp(z);
-    const double a00 = -cm.fx * iz, a02 = cm.fx * x * iz * iz, a11 = -cm.fy * iz, a12 = cm.fy * y * iz * iz;
-#pragma unroll
-    for (int q = 0; q < 3; ++q) { P[0][q] = a00 * R[q] + a02 * R[6 + q]; P[1][q] = a11 * R[3 + q] + a12 * R[6 + q]; }
-    C[0][0] = a02 * y; C[0][1] = a00 * z - a02 * x; C[0][2] = -a00 * y; C[0][3] = a00; C[0][4] = 0.0; C[0][5] = a02;
-    C[1][0] = -a11 * z + a12 * y; C[1][1] = -a12 * x; C[1][2] = a11 * x; C[1][3] = 0.0; C[1][4] = a11; C[1][5] = a12;
-    if (NR == 3) {
-        const double m = stereo ? 1.0 : 0.0;
-        const double c00 = m * a00, c02 = m * (a02 - cm.bf * iz * iz);
-#pragma unroll
-        for (int q = 0; q < 3; ++q) P[NR - 1][q] = c00 * R[q] + c02 * R[6 + q];
-        C[NR - 1][0] = c02 * y; C[NR - 1][1] = c00 * z - c02 * x; C[NR - 1][2] = -c00 * y;
-        C[NR - 1][3] = c00; C[NR - 1][4] = 0.0; C[NR - 1][5] = c02;
-    }
-}
+// (the Jacobian rows of one edge from its cached camera-frame point: edge_rows of edge_model.h)
 
 // accumulates one diagonal-pair entry: ha += w C^T C (Hpp), ba += C^T (-w e) (b_p) and, unless HPP_ONLY, the Schur
 // terms sa += B Dinv B^T, ca += B Dinv b_l.  `wg` = 0 masks the entry out (all its contributions are exact zeros).
@@ -901,7 +864,7 @@ __device__ __forceinline__ void lambda_init_body(const DevWindow &w)
     m = wave_max(m);
     F = wave_sum_dpp(F);
     if (lane == 0) {
-        c->lambda = 1e-5 * m;
+        c->lambda = lm_lambda_init(m);
         c->nu = 2.0;
         c->F0 = F;
         c->cost0 = F;
@@ -930,15 +893,11 @@ __device__ __forceinline__ void finalize_body(const DevWindow &w, int bid, int n
         // from the back-substitution)
         double chi2;
         {
-            const double *Rs = w.st[sel].Rt + 12 * w.g_pose[g];
-            const double *Xs = w.st[sel].point + 3 * w.g_point[g];
-            const double x = Rs[0] * Xs[0] + Rs[1] * Xs[1] + Rs[2] * Xs[2] + Rs[9];
-            const double y = Rs[3] * Xs[0] + Rs[4] * Xs[1] + Rs[5] * Xs[2] + Rs[10];
-            const double z = Rs[6] * Xs[0] + Rs[7] * Xs[1] + Rs[8] * Xs[2] + Rs[11];
+            double x, y, z;
+            cam_point(w.st[sel].Rt + 12 * w.g_pose[g], w.st[sel].point + 3 * w.g_point[g], x, y, z);
             const double om = w.isig[g];
             const Cam cm = cam_of_rt(w, w.g_pose[g]);
-            const double e0 = w.obs[2 * g] - (cm.fx * x / z + cm.cx), e1 = w.obs[2 * g + 1] - (cm.fy * y / z + cm.cy);
-            chi2 = e0 * (om * e0) + e1 * (om * e1);
+            chi2 = edge_chi2_div(cm, x, y, z, w.obs + 2 * g, om);
             if (w.stereo) {
                 const double ur = w.obs_r[g];
                 if (ur >= 0.0) { const double e2 = ur - (cm.fx * x / z + cm.cx - cm.bf / z); chi2 += e2 * (om * e2); }

@@ -64,7 +64,8 @@ __device__ __forceinline__ double sig_at(const double *sig, int r, int c)
 }
 
 // B_il^T (3 x 6) of grouped edge g at the state the linearisation left (its edge record: camera-frame point and weight), the
-// Jacobian rows of k_schur's edge_rows (kernels.hip); false for an edge of a keyframe outside the system (fixed)
+// Jacobian rows of k_schur's edge_rows (edge_model.h) written out: through the call two v_mul_f64 of k_marg_out swap their
+// operands, and movba_lba_marginals measured slower at cfg2; false for an edge of a keyframe outside the system (fixed)
 __device__ __forceinline__ bool edge_g(const DevWindow &w, const DevState &S, int g, double (&G)[3][6], int &h)
 {
     const int ip = w.g_pose[g];

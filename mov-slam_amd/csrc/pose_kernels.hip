@@ -12,6 +12,8 @@
 #include <cmath>
 
 #include "device_math.h"
+#include "edge_model.h"
+#include "lm_rule.h"
 #include "magsac.h"
 #include "movba.h"
 #include "pose_kernels.h"
@@ -228,13 +230,11 @@ __device__ void hyp_score(const PoseDev &p, const double *Xw, const double *obs,
         const Magsac ms(p.chi2_gate);
         const double *R = cand + (size_t)cidx * 12;
         for (int i = lane; i < p.n; i += 64) {
-            const double X0 = Xw[3 * i], X1 = Xw[3 * i + 1], X2 = Xw[3 * i + 2];
-            const double x = R[0] * X0 + R[1] * X1 + R[2] * X2 + R[9];
-            const double y = R[3] * X0 + R[4] * X1 + R[5] * X2 + R[10];
-            const double z = R[6] * X0 + R[7] * X1 + R[8] * X2 + R[11];
+            const double X[3] = { Xw[3 * i], Xw[3 * i + 1], Xw[3 * i + 2] };
+            double x, y, z;
+            cam_point(R, X, x, y, z);
             const double om = isig[i];
-            const double e0 = obs[2 * i] - (p.fx * x / z + p.cx), e1 = obs[2 * i + 1] - (p.fy * y / z + p.cy);
-            const double chi2 = e0 * (om * e0) + e1 * (om * e1);
+            const double chi2 = edge_chi2_div(p, x, y, z, obs + 2 * i, om);
             const bool in = (z > 0.0) && (chi2 <= p.chi2_gate);
             double ls, wt;
             ms.terms(chi2, z > 0.0, p.chi2_gate, ls, wt);
@@ -409,12 +409,14 @@ __device__ __forceinline__ void pose_opt_body(const PoseDev &p)
             for (int u = 0; u < kFly; ++u) {
                 if (w0 + u * kT >= p.n) break;
                 const double X0 = b.X[u][0], X1 = b.X[u][1], X2 = b.X[u][2];
-                const bool in = b.in[u];
+                const bool in = b.in[u];            // (cam_point written out inside the selects: a select behind the call is another stream)
                 const double x = in ? R[0] * X0 + R[1] * X1 + R[2] * X2 + R[9] : 0.0;
                 const double y = in ? R[3] * X0 + R[4] * X1 + R[5] * X2 + R[10] : 0.0;
                 const double z = in ? R[6] * X0 + R[7] * X1 + R[8] * X2 + R[11] : 1.0;
                 const double om = in ? b.om[u] : 0.0;
                 const double iz = fast_rcp(z);
+                // (not edge_res_rcp: here the product with iz fuses with the add of the principal point, and not huber_rs: the
+                //  sqrt form - both round otherwise)
                 const double e0 = b.o[u][0] - (p.fx * x * iz + p.cx), e1 = b.o[u][1] - (p.fy * y * iz + p.cy);
                 const double chi2 = e0 * (om * e0) + e1 * (om * e1);
                 F[0] += (robust && p.huber_delta > 0.0 && !(chi2 <= dsqr)) ? 2.0 * sqrt(chi2) * p.huber_delta - dsqr : chi2;
@@ -450,16 +452,16 @@ __device__ __forceinline__ void pose_opt_body(const PoseDev &p)
               for (int u = 0; u < kFly; ++u) {
                 if (w0 + u * kT >= p.n) break;
                 const double X0 = b.X[u][0], X1 = b.X[u][1], X2 = b.X[u][2];
-                const bool in = b.in[u];
+                const bool in = b.in[u];            // (cam_point written out inside the selects: a select behind the call is another stream)
                 const double x = in ? R[0] * X0 + R[1] * X1 + R[2] * X2 + R[9] : 0.0;
                 const double y = in ? R[3] * X0 + R[4] * X1 + R[5] * X2 + R[10] : 0.0;
                 const double z = in ? R[6] * X0 + R[7] * X1 + R[8] * X2 + R[11] : 1.0;
                 const double om = in ? b.om[u] : 0.0;
-                // (one reciprocal per match and pass instead of six divisions)
-                const double iz = fast_rcp(z), uu = p.fx * x * iz, vv = p.fy * y * iz;
-                const double e0 = b.o[u][0] - (uu + p.cx), e1 = b.o[u][1] - (vv + p.cy);
-                const double chi2 = e0 * (om * e0) + e1 * (om * e1);
+                const double iz = fast_rcp(z);
+                double uu, vv, e0, e1;
+                const double chi2 = edge_res_rcp(p, x, y, iz, b.o[u], om, uu, vv, e0, e1);
                 double rho0 = chi2, rho1 = 1.0;
+                // (huber_rs of edge_model.h with `robust` in its condition: behind `if (robust)` the stream changes)
                 if (robust && p.huber_delta > 0.0 && !(chi2 <= dsqr)) {
                     const double rs = rsqrt(chi2), sq = chi2 > DBL_MAX ? chi2 : chi2 * rs;       // (sqrt(inf) = inf, not inf * 0)
                     rho0 = 2.0 * sq * p.huber_delta - dsqr; rho1 = p.huber_delta * rs;
@@ -496,7 +498,7 @@ __device__ __forceinline__ void pose_opt_body(const PoseDev &p)
                 double md = 0.0;
 #pragma unroll
                 for (int a = 0; a < 6; ++a) md = fmax(md, fabs(acc[a * 6 - a * (a - 1) / 2]));
-                lambda = 1e-5 * md; ni = 2.0;
+                lambda = lm_lambda_init(md); ni = 2.0;
             }
             double rho = 0.0;
             int qmax = 0;
@@ -509,6 +511,8 @@ __device__ __forceinline__ void pose_opt_body(const PoseDev &p)
                 STAMP_SEG(pseg, 2);
                 double F1 = cost(pose, robust);
                 STAMP_SEG(pseg, 3);
+                // (lm_gain, the rejection of lm_update and the two loop conditions of lm_rule.h written out, here and below: through
+                //  the calls all four k_pose_opt kernels change their instruction count)
                 if (!ok2) F1 = DBL_MAX;
                 double scale = 1e-3;
                 if (ok2) {
@@ -518,11 +522,8 @@ __device__ __forceinline__ void pose_opt_body(const PoseDev &p)
                     scale += s;
                 }
                 rho = (F0 - F1) / scale;
-                if (rho > 0.0 && isfinite(F1)) {
-                    const double tr = 2.0 * rho - 1.0;
-                    double alpha = 1.0 - tr * tr * tr;           // (pow(tmp, 3) in g2o)
-                    alpha = fmin(alpha, 2.0 / 3.0);
-                    lambda *= fmax(1.0 / 3.0, alpha); ni = 2.0; F0 = F1;
+                if (lm_accept(rho, F1)) {
+                    lm_update(true, rho, lambda, ni); F0 = F1;
                 } else {
                     lambda *= ni; ni *= 2.0;
 #pragma unroll
@@ -542,13 +543,11 @@ __device__ __forceinline__ void pose_opt_body(const PoseDev &p)
         q2R(T, R);
         double sc[2] = { 0.0, 0.0 };
         for (int i = tid; i < p.n; i += kT) {
-            const double X0 = Xw[3 * i], X1 = Xw[3 * i + 1], X2 = Xw[3 * i + 2];
-            const double x = R[0] * X0 + R[1] * X1 + R[2] * X2 + R[9];
-            const double y = R[3] * X0 + R[4] * X1 + R[5] * X2 + R[10];
-            const double z = R[6] * X0 + R[7] * X1 + R[8] * X2 + R[11];
+            const double X[3] = { Xw[3 * i], Xw[3 * i + 1], Xw[3 * i + 2] };
+            double x, y, z;
+            cam_point(R, X, x, y, z);
             const double om = isig[i];
-            const double e0 = obs[2 * i] - (p.fx * x / z + p.cx), e1 = obs[2 * i + 1] - (p.fy * y / z + p.cy);
-            const double chi2 = e0 * (om * e0) + e1 * (om * e1);
+            const double chi2 = edge_chi2_div(p, x, y, z, obs + 2 * i, om);
             const bool in = (z > 0.0) && (chi2 <= p.chi2_gate);
             double ls, wt;
             ms.terms(chi2, z > 0.0, p.chi2_gate, ls, wt);
@@ -595,6 +594,8 @@ __device__ __forceinline__ void pose_opt_body(const PoseDev &p)
         double nb[1] = { 0.0 };
         __syncthreads();
         for (int i = tid; i < p.n; i += kT) {
+            // (cam_point and edge_chi2_div of edge_model.h written out: through the calls the zero-initialisations in front of
+            //  k_pose_opt's system pass are issued in another order)
             const double X0 = Xw[3 * i], X1 = Xw[3 * i + 1], X2 = Xw[3 * i + 2];
             const double x = R[0] * X0 + R[1] * X1 + R[2] * X2 + R[9];
             const double y = R[3] * X0 + R[4] * X1 + R[5] * X2 + R[10];

@@ -1,6 +1,6 @@
 // The bundle adjustment of movba_init_map (stage 2, include/movba.h) on the CPU: the library's own per-point arithmetic
-// (init_map.h: im_linearize, im_schur, im_back, im_cost - the code k_init_map inlines) with the points summed serially by one
-// thread.  What surrounds that arithmetic is this file's own, written for the host: a plain 6 x 6 Cholesky, the quaternion to matrix
+// (init_map.h: im_linearize, im_schur, im_back, im_cost - the code k_init_map inlines - and the step rule of lm_rule.h) with the
+// points summed serially by one thread.  What surrounds that arithmetic is this file's own, written for the host: a plain 6 x 6 Cholesky, the quaternion to matrix
 // conversion and SE3Quat's exponential as SURVEY A.8 writes it - NOT device_math.h's solve6 and se3_oplus, which the kernel uses
 // and which only the GPU tests exercise.  tests/test_init_map_cpu.py builds this file with the host compiler against the
 // stand-in runtime header of tests/hipstub and compares what it prints with the oracle.
@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "init_map.h"
+#include "lm_rule.h"
 #include "movba.h"
 
 using namespace movba;
@@ -124,10 +125,11 @@ int main(int argc, char **argv)
         double F0 = acc[27];
         if (it == 0) {
             for (int a = 0; a < 6; ++a) md = std::fmax(std::fabs(acc[a * 6 - a * (a - 1) / 2]), md);
-            lambda = 1e-5 * md; ni = 2.0; cost0 = F0;
+            lambda = lm_lambda_init(md); ni = 2.0; cost0 = F0;
         }
         double rho = 0.0;
         int qmax = 0;
+        bool lambda_ok = true;
         do {
             double sc[27] = { 0.0 }, Su[21], bS[6], xp[6], trial[7], Rt[9];
             for (int k = 0; k < n; ++k) im_schur(&lin[(size_t)kImLin * k], lambda, sc);
@@ -148,28 +150,22 @@ int main(int argc, char **argv)
                 }
                 F1 += im_cost(Rt, trial + 4, cam, huber, &X[3 * k], &o1[2 * k], &o2[2 * k], s1[k], s2[k], c2);
             }
-            if (!ok2) { F1 = DBL_MAX; ++chol_fail; }
-            scale += 1e-3;
-            rho = (F0 - F1) / scale;
-            const bool accept = rho > 0.0 && std::isfinite(F1);
+            if (!ok2) ++chol_fail;
+            const LmGain gain = lm_gain(F0, F1, scale, ok2);
+            F1 = gain.F1; rho = gain.rho;
+            const bool accept = lm_accept(rho, F1);
             trace.insert(trace.end(), { lambda, F0, F1, rho, accept ? 1.0 : 0.0 });
-            bool lambda_ok = true;
+            lambda_ok = lm_update(accept, rho, lambda, ni);
             if (accept) {
-                double alpha = 2.0 * rho - 1.0;
-                alpha = 1.0 - alpha * alpha * alpha;
-                lambda *= std::fmax(1.0 / 3.0, std::fmin(alpha, 2.0 / 3.0));
-                ni = 2.0; F0 = F1;
+                F0 = F1;
                 for (int e = 0; e < 7; ++e) pose[e] = trial[e];
             } else {
-                lambda *= ni; ni *= 2.0;
                 X = Xbk;
-                lambda_ok = std::isfinite(lambda);
             }
             ++solves; ++qmax;
-            if (!lambda_ok) break;
-        } while (rho < 0.0 && qmax < max_trials);
+        } while (lm_more_trials(rho, qmax, max_trials, lambda_ok));
         iters = it + 1;
-        if (qmax == max_trials || rho == 0.0 || !std::isfinite(lambda)) ok = false;
+        if (lm_terminate(rho, qmax, max_trials, lambda_ok)) ok = false;
     }
     q2R(pose, R);
     double cost = 0.0;
