@@ -987,6 +987,99 @@ typedef struct {
  * reuses the staging buffer: the window, its results, its marginals and later runs stay as they were. */
 int  movba_track_match(movba_handle *h, const movba_track_desc *desc, movba_track_result *res);
 
+/* EXPRESS detection and descriptors for many frames per call: the pixel arithmetic of MOVExtractor::operator()
+ * (MOVExtractor.cc:63-455), which is the EXPRESS code of EXPRESS.h:79-192 - compute_center, compute_descriptor, compute_express,
+ * compute_distance - block by block: about 8 000 blocks for a 1080p intra frame or a low-coverage frame (extract_moves, :37-61,
+ * :123-156, :418-451), a few thousand for an inter frame (:254-334, :380-416).  It is what produces VideoFeature::trackId's
+ * carriers and mvKeysUn[j].pt, which movba_track_match and movba_triangulate take.  Everything is integer: the result is exact.
+ * cv::calcOpticalFlowPyrLK (:91, :196, :347) is not part of it. */
+#define MOVBA_EX_DETECT   0   /* compute_express, then compute_descriptor where it returns true (:50-52, :132-134, :391-395) */
+#define MOVBA_EX_DESCRIBE 1   /* compute_descriptor alone (:223, :290, :313)                                                 */
+#define MOVBA_MAX_EXPRESS_IMAGES 1024
+#define MOVBA_MAX_EXPRESS_ITEMS  4194304   /* 2^22 */
+/* movba_express_result::code, in the order the reference tests */
+#define MOVBA_EX_FEATURE      1   /* DETECT passed, descriptor written                                                       */
+#define MOVBA_EX_DESCRIBED    2   /* DESCRIBE, descriptor written                                                            */
+#define MOVBA_EX_REJ_BOUNDS  16   /* the reference's `if` failed: !(x >= 0 && y >= 0 && x + w < cols && y + h < rows), strict
+                                     as written: a block that touches the last column or row is rejected                     */
+#define MOVBA_EX_REJ_SHAPE   17   /* (w, h) is not one of 8x8, 16x8, 8x16, 16x16: diagonal() handles no other shape and the
+                                     reference reads garbage there                                                           */
+#define MOVBA_EX_REJ_FLAT    18   /* the precheck failed                                                                     */
+#define MOVBA_EX_REJ_NO_EDGE 19   /* neither diagonal pass succeeded                                                         */
+
+typedef struct {
+    int32_t n_images, pad;
+    const uint8_t *const *image;    /* n_images pointers to 8-bit grey pixels (imGray, CV_8UC1); may be NULL for an image without
+                                       items                                                                                */
+    const int32_t *rows, *cols;     /* n_images each, >= 1; the sum of rows * cols over the images is at most 2^28          */
+    const int32_t *stride;          /* n_images: bytes from one row to the next, >= cols; only the first cols bytes of a row are
+                                       read                                                                                 */
+    const int32_t *threshold;       /* n_images: 0 .. 255 (MOVExtractor.threshold: 25 and 40 in the shipped configurations) */
+    const int32_t *item_ptr;        /* n_images + 1, ascending, [0] = 0: the items of image i are [item_ptr[i], item_ptr[i + 1]);
+                                       n_items = item_ptr[n_images] <= MOVBA_MAX_EXPRESS_ITEMS                              */
+    const int32_t *item_rect;       /* n_items x 4: x y w h = cv::Rect; w is img.cols, h is img.rows of the block           */
+    const int32_t *item_mode;       /* n_items: MOVBA_EX_*                                                                  */
+    const uint64_t *item_ref;       /* n_items x 4 or NULL: the descriptor to measure against (pvf.desc, :291, :314)        */
+} movba_express_desc;   /* 80 bytes */
+
+typedef struct {
+    uint8_t  *code;                 /* n_items: MOVBA_EX_*                                                                  */
+    uint64_t *desc;                 /* n_items x 4: bit k of the bitset<256> is bit k & 63 of word k >> 6; zeros where none was
+                                       computed                                                                             */
+    int32_t  *count;                /* n_items: desc.count(), the sort key at :252; -1 where no descriptor was computed     */
+    int32_t  *distance;             /* n_items or NULL: compute_distance(item_ref, desc); -1 without a descriptor or without
+                                       item_ref                                                                             */
+    int32_t  *n_features;           /* n_images: the items of the image with MOVBA_EX_FEATURE                               */
+    int32_t   status, pad;
+} movba_express_result; /* 48 bytes */
+
+/* Restated as written, quirks included, item by item.  I is the item's image, (x0, y0, w, h) its rect.
+ *   Tests    MOVBA_EX_REJ_BOUNDS, then MOVBA_EX_REJ_SHAPE; neither kind of rectangle is ever read.
+ *   Centre   r = w / 2, c = h / 2.  compute_center hands at<>() its arguments swapped, so r - from the WIDTH - is the ROW offset
+ *            and c - from the HEIGHT - is the COLUMN offset: center = (I(y0+r, x0+c) + I(y0+r-1, x0+c-1) + I(y0+r, x0+c-1) +
+ *            I(y0+r-1, x0+c)) / 4, the integer quotient.  On 16x8 and 8x16 blocks this reads one pixel right of, or below, the
+ *            block; the bounds test keeps it inside the image.
+ *   Bounds   low = (center - threshold) mod 256, high = (center + threshold) mod 256 (uint8 wrap-around);
+ *            outside(p) = low > p || high < p.
+ *   Shifted  the descriptor and the precheck read s(y, x) = I(y0 + y, x0 + x + 1): the `p++` in front of the read (:103, :130).
+ *            Descriptor: bit y * h + x (img.rows, not img.cols) is set for outside(s(y, x)), y < h, x < w; where w = 16 and
+ *            h = 8 the indices overlap and are OR-ed.  Precheck: passes when the number of outside shifted pixels is at least
+ *            (uint8)(h * w * 0.125); the row-wise early `break` only keeps the uint8 counter from wrapping, the decision is the
+ *            full count's.
+ *   Votes    read the TRUE pixels t(y, x) = I(y0 + y, x0 + x).  slices = h + w - 1; diagonal i of pass 0 is {(y, x): x - y =
+ *            i - (h - 1)}, of pass 1 {(y, x): (w - 1 - x) - y = i - (h - 1)} (what the tables at EXPRESS.h:20-38 encode).
+ *            rounds = round(0.25 * slices) = 4, 6, 6, 8; u_rounds = slices - rounds.  Per pass wins = losses = 0; for i = 0 ..
+ *            slices - 1: win = the outside pixels on the diagonal, loss = its length - win;
+ *            if wins < rounds: wins = (win >= loss) ? wins + 1 : 0; if losses < rounds: losses = (loss > win) ? losses + 1 : 0;
+ *            break when i > u_rounds && (wins == 0 || losses == 0).  The pass succeeds when wins >= rounds && losses >= rounds;
+ *            pass 1 runs only if pass 0 failed.
+ *   DETECT   MOVBA_EX_REJ_FLAT when the precheck fails, else MOVBA_EX_REJ_NO_EDGE when both passes fail, else
+ *            MOVBA_EX_FEATURE with the descriptor.  DESCRIBE: MOVBA_EX_DESCRIBED with the descriptor, no other test.
+ *   count    desc.count(); distance = (item_ref ^ desc).count().
+ * What stays with the caller: mCurrentId, the lbFound bookkeeping (order-dependent), the float-to-int truncation that makes a
+ * cv::Rect, the LK calls and the sort at :249.
+ * An item's result depends on its rect, its mode, its item_ref and its image alone - not on other items, other images, their
+ * order, or how they are split over calls - and two calls give the same bits.
+ * Returns MOVBA_ERR_ARG for a NULL handle, descriptor or result; n_images negative or above MOVBA_MAX_EXPRESS_IMAGES; item_ptr
+ * NULL, not ascending, not starting at 0 or ending above MOVBA_MAX_EXPRESS_ITEMS; a NULL array that the counts make necessary
+ * (image, rows, cols, stride, threshold, item_rect, item_mode, code, desc, count, n_features when n_items > 0); a NULL image
+ * pointer for an image that has items; rows or cols below 1, stride < cols, or a sum of rows * cols above 2^28; a threshold
+ * outside 0 .. 255; an unknown mode.  MOVBA_ERR_HIP as elsewhere.  Every argument is checked before anything is queued, and on a
+ * non-zero status nothing is written except `status`.  n_images == 0, or no items at all: MOVBA_OK and nothing else written.
+ * One packed copy to the device - the pixels of the images that have items go tightly, row by row without the stride's padding -
+ * two launches - k_express, one wavefront per item, then k_express_counts, which hands the per-image counts over - and one
+ * synchronisation; result arrays that lie in movba_host_alloc memory are written by the kernels themselves.  May share a handle
+ * with an uploaded or solved window, waiting for the window's arrays before it reuses the staging buffer: the window, its
+ * results, its marginals and later runs stay as they were. */
+int  movba_express(movba_handle *h, const movba_express_desc *desc, movba_express_result *res);
+/* The lattice of extract_moves (host only, no device): for y = 8; y < rows - 8; y += 16, and inside that x = 8; x < cols - 8;
+ * x += 16, the rect (x - 8, y - 8, 16, 16), in that order; the keypoint of a rect is (x, y).  Writes the first `cap` of them
+ * (x y w h) to `rects` and returns the number of rects of the lattice, which may be larger than cap (rects may be NULL when cap
+ * is 0); 0 for an image of 16 or fewer rows or columns.  The bounds test is left to movba_express (the loop's own bounds
+ * already keep every rect of the lattice inside it: an image of 240 x 320 has 14 x 19 rects).  MOVBA_ERR_ARG for a negative cap, rects NULL
+ * with cap > 0, or a lattice of more than 2^31 - 1 rects. */
+int  movba_express_grid(int32_t rows, int32_t cols, int32_t *rects, int32_t cap);
+
 #ifdef __cplusplus
 }
 #endif

@@ -26,6 +26,7 @@ FLAG_STALE_ERROR_QUIRK = 1
 _d = C.POINTER(C.c_double)
 _i = C.POINTER(C.c_int32)
 _u = C.POINTER(C.c_uint8)
+_q = C.POINTER(C.c_uint64)
 
 
 class MovbaError(RuntimeError):
@@ -179,6 +180,23 @@ class TrackResult(C.Structure):
                 ("depth1", _d), ("depth2", _d), ("item_slot", _i), ("n_found", _i), ("n_matches", C.c_int32), ("status", C.c_int32)]
 
 
+class ExpressDesc(C.Structure):
+    _fields_ = [("n_images", C.c_int32), ("pad", C.c_int32), ("image", C.POINTER(C.c_void_p)), ("rows", _i), ("cols", _i),
+                ("stride", _i), ("threshold", _i), ("item_ptr", _i), ("item_rect", _i), ("item_mode", _i), ("item_ref", _q)]
+
+
+class ExpressResult(C.Structure):
+    _fields_ = [("code", _u), ("desc", _q), ("count", _i), ("distance", _i), ("n_features", _i), ("status", C.c_int32),
+                ("pad", C.c_int32)]
+
+
+# movba_express_desc::item_mode and movba_express_result::code (MOVBA_EX_*)
+EX_DETECT, EX_DESCRIBE = 0, 1
+EX_FEATURE, EX_DESCRIBED = 1, 2
+EX_REJ_BOUNDS, EX_REJ_SHAPE, EX_REJ_FLAT, EX_REJ_NO_EDGE = range(16, 20)
+MAX_EXPRESS_IMAGES = 1024
+MAX_EXPRESS_ITEMS = 1 << 22
+EXPRESS_ARRAYS = (("code", np.uint8, 1), ("desc", np.uint64, 4), ("count", np.int32, 1), ("distance", np.int32, 1))
 # movba_track_desc::query_mode (MOVBA_TM_*)
 TM_TRIANGULATION, TM_LOOKUP = 0, 1
 MAX_TRACK_SLOTS = 16384
@@ -223,7 +241,8 @@ EXPORTS = ["movba_version", "movba_status_string", "movba_create", "movba_destro
            "movba_structure_probe", "movba_pose_opt", "movba_set_profile_mask", "movba_lba_run_batch", "movba_pose_ransac_samples",
            "movba_host_alloc", "movba_host_free", "movba_dense_plan_probe", "movba_pose_opt_batch", "movba_lba_marginals", "movba_triangulate",
            "movba_two_view", "movba_two_view_samples", "movba_two_view_lo", "movba_init_map", "movba_view_points",
-           "movba_point_normals", "movba_lba_point_normals", "movba_covisibility", "movba_track_match"]
+           "movba_point_normals", "movba_lba_point_normals", "movba_covisibility", "movba_track_match", "movba_express",
+           "movba_express_grid"]
 
 _libs = {False: None, True: None}
 
@@ -289,6 +308,8 @@ def lib(hooks: bool = False):
         L.movba_lba_point_normals.argtypes = [C.c_void_p, _i, _i, _d, C.c_int32, _u, _d, _d, _d]
         L.movba_covisibility.argtypes = [C.c_void_p, C.POINTER(CovisDesc), C.POINTER(CovisResult)]
         L.movba_track_match.argtypes = [C.c_void_p, C.POINTER(TrackDesc), C.POINTER(TrackResult)]
+        L.movba_express.argtypes = [C.c_void_p, C.POINTER(ExpressDesc), C.POINTER(ExpressResult)]
+        L.movba_express_grid.argtypes = [C.c_int32, C.c_int32, _i, C.c_int32]
         L.movba_host_alloc.argtypes = [C.c_size_t]
         L.movba_host_alloc.restype = C.c_void_p
         L.movba_dense_plan_probe.argtypes = [C.c_int32, C.c_int32, C.c_int32, _i, _i, C.c_int32, _i, C.c_int32]
@@ -671,6 +692,67 @@ def track_result(n_queries, n_items, match_cap, payload=(), alloc=np.zeros):
     for key in payload:
         keep[key] = alloc((match_cap, 2) if key.startswith("obs") else (match_cap,), np.float64)
         setattr(r, key, _p(keep[key], _d))
+    return r, keep
+
+
+def express_grid(rows: int, cols: int) -> np.ndarray:
+    """movba_express_grid (host only): the lattice of extract_moves over an image of rows x cols, (n, 4) int32 x y w h; the
+    keypoint of a rect is (x + 8, y + 8)."""
+    n = lib().movba_express_grid(rows, cols, None, 0)
+    if n < 0:
+        raise MovbaError(f"movba_express_grid: {status_string(n)}")
+    out = np.zeros((n, 4), np.int32)
+    if n and lib().movba_express_grid(rows, cols, _p(out, _i), n) != n:
+        raise MovbaError("movba_express_grid: the count changed between two calls")
+    return out
+
+
+def express_desc(images, items, thresholds, refs=None):
+    """images: one 2-D uint8 array per image (any row stride, unit column stride), or None for an image without items (it goes as
+    a NULL pointer of 1 x 1); items: per image (rects (n, 4) x y w h, modes (n,) or one mode); thresholds: one per image or one
+    for all; refs: None, or per image (n, 4) uint64 -> (movba_express_desc, the arrays it points into)."""
+    ni = len(images)
+    thresholds = np.broadcast_to(np.asarray(thresholds, np.int32), (ni,)) if ni else np.zeros(0, np.int32)
+    keep = dict(images=[], rows=np.ones(ni, np.int32), cols=np.ones(ni, np.int32), stride=np.ones(ni, np.int32),
+                threshold=np.array(thresholds, np.int32), image=(C.c_void_p * max(ni, 1))())
+    rects, modes = [], []
+    for i, (im, it) in enumerate(zip(images, items)):
+        if im is not None:
+            if im.dtype != np.uint8 or im.ndim != 2 or (im.shape[1] > 1 and im.strides[1] != 1):
+                raise ValueError("express_desc: an image is a 2-D uint8 array whose rows are contiguous")
+            keep["images"].append(im)
+            keep["image"][i] = im.ctypes.data
+            keep["rows"][i], keep["cols"][i] = im.shape
+            keep["stride"][i] = im.strides[0] if im.shape[0] > 1 else im.shape[1]
+        r = np.asarray(it[0], np.int32).reshape(-1, 4)
+        rects.append(r)
+        modes.append(np.broadcast_to(np.asarray(it[1], np.int32), (len(r),)))
+    keep["item_ptr"] = np.concatenate([[0], np.cumsum([len(r) for r in rects])]).astype(np.int32)
+    keep["item_rect"] = np.ascontiguousarray(np.concatenate(rects) if rects else np.zeros((0, 4)), np.int32)
+    keep["item_mode"] = np.ascontiguousarray(np.concatenate(modes) if modes else np.zeros(0), np.int32)
+    d = ExpressDesc()
+    d.n_images = ni
+    d.image = C.cast(keep["image"], C.POINTER(C.c_void_p))
+    for key in ("rows", "cols", "stride", "threshold", "item_ptr", "item_rect", "item_mode"):
+        setattr(d, key, _p(keep[key], _i))
+    if refs is not None:
+        parts = [np.asarray(r, np.uint64).reshape(-1, 4) for r in refs]
+        keep["item_ref"] = np.ascontiguousarray(np.concatenate(parts) if parts else np.zeros((0, 4)), np.uint64)
+        if len(keep["item_ref"]) != len(keep["item_rect"]):
+            raise ValueError("express_desc: refs holds one descriptor per item")
+        d.item_ref = _p(keep["item_ref"], _q)
+    return d, keep
+
+
+def express_result(n_items, n_images, alloc=np.zeros, distance=True):
+    """-> (movba_express_result with its output arrays, the arrays it points into)"""
+    keep = {key: alloc((n_items, width) if width > 1 else (n_items,), dtype) for key, dtype, width in EXPRESS_ARRAYS
+            if distance or key != "distance"}
+    keep["n_features"] = alloc((n_images,), np.int32)
+    r = ExpressResult()
+    r.code = _p(keep["code"], _u); r.desc = _p(keep["desc"], _q); r.count = _p(keep["count"], _i); r.n_features = _p(keep["n_features"], _i)
+    if distance:
+        r.distance = _p(keep["distance"], _i)
     return r, keep
 
 
@@ -1086,6 +1168,18 @@ class Solver:
         return dict(status=rc, n_matches=r.n_matches, pair_ptr=out["pair_ptr"], pairs=dict(pair_view=keep["query_view"], pair_ptr=out["pair_ptr"]),
                     matches={key: out[key] for key in payload}, match_slot1=out["match_slot1"], match_slot2=out["match_slot2"],
                     item_slot=out["item_slot"], query_ptr=keep["query_ptr"], n_found=out["n_found"])
+
+    def express(self, images, items, thresholds, refs=None, pinned=False) -> dict:
+        """movba_express (EXPRESS detection and descriptors, the pixel arithmetic of MOVExtractor): arguments as express_desc
+        -> dict(status, code (n,) uint8, desc (n, 4) uint64, count, distance (n,), n_features (n_images,), item_ptr).  pinned:
+        result arrays in movba_host_alloc memory, written by the kernels themselves."""
+        d, keep = express_desc(images, items, thresholds, refs)
+        r, out = express_result(len(keep["item_rect"]), d.n_images, self._pinned if pinned else np.zeros)
+        rc = self._L.movba_express(self._h, C.byref(d), C.byref(r))
+        if rc < 0:
+            raise MovbaError(f"movba_express: {status_string(rc)}")
+        out.update(status=rc, item_ptr=keep["item_ptr"])
+        return out
 
     def lba_point_normals(self, ref_pose, ref_level, scale_factors, outlier=None, pinned=False) -> dict:
         """movba_lba_point_normals: the same quantities for every map point of the window of the last run, read where it lies
