@@ -1056,8 +1056,9 @@ typedef struct {
  *   DETECT   MOVBA_EX_REJ_FLAT when the precheck fails, else MOVBA_EX_REJ_NO_EDGE when both passes fail, else
  *            MOVBA_EX_FEATURE with the descriptor.  DESCRIBE: MOVBA_EX_DESCRIBED with the descriptor, no other test.
  *   count    desc.count(); distance = (item_ref ^ desc).count().
- * What stays with the caller: mCurrentId, the lbFound bookkeeping (order-dependent), the float-to-int truncation that makes a
- * cv::Rect, the LK calls and the sort at :249.
+ * What stays with the caller of THIS call: mCurrentId, the lbFound bookkeeping (order-dependent), the float-to-int truncation
+ * that makes a cv::Rect, the sort at :249 - all of which movba_advance, below, does for an inter frame - and the LK calls
+ * (INTEGRATION.md).
  * An item's result depends on its rect, its mode, its item_ref and its image alone - not on other items, other images, their
  * order, or how they are split over calls - and two calls give the same bits.
  * Returns MOVBA_ERR_ARG for a NULL handle, descriptor or result; n_images negative or above MOVBA_MAX_EXPRESS_IMAGES; item_ptr
@@ -1079,6 +1080,124 @@ int  movba_express(movba_handle *h, const movba_express_desc *desc, movba_expres
  * already keep every rect of the lattice inside it: an image of 240 x 320 has 14 x 19 rects).  MOVBA_ERR_ARG for a negative cap, rects NULL
  * with cap > 0, or a lattice of more than 2^31 - 1 rects. */
 int  movba_express_grid(int32_t rows, int32_t cols, int32_t *rects, int32_t cap);
+
+/* The inter-frame walk of MOVExtractor::operator() for many frames (streams) per call: from the previous frame's features, the
+ * frame's motion vectors and macroblocks to the frame's _vf segments with their track ids (MOVExtractor.cc:245-335, :380-451) -
+ * the sort at :249, the choice among up to four motion vectors, the float-to-int truncation that makes a cv::Rect, the lbFound
+ * claims of :306-309, the dist <= 40 gate, the new macroblocks, mov_cnt, the grid of :418-451 and mCurrentId.  It is what
+ * produces VideoFeature::trackId, the join key of movba_track_match.  Everything is integer except one fp32 add and one fp32
+ * subtract per rectangle: the result is exact.  cv::calcOpticalFlowPyrLK (:91, :196, :347), the I-frame path and the
+ * relocalisation block (:161-243) are not part of it. */
+#define MOVBA_MAX_ADVANCE_PREV 16384   /* previous features of one frame: what one workgroup sorts in LDS (8-byte keys, 128 KiB) */
+/* movba_advance_result::fate */
+#define MOVBA_ADV_KEPT        1   /* arrived, won its claim (or claimed nothing), dist <= 40: a feature of the kept segment     */
+#define MOVBA_ADV_COVERAGE    2   /* prev_coverage != 0: covFeat, handed back untouched for the caller's LK call (:337-377)     */
+#define MOVBA_ADV_NO_MV      16   /* cand[0] == -1: no motion vector reaches the feature                                       */
+#define MOVBA_ADV_REJ_BOUNDS 17   /* the final rect fails movba_express's bounds test; it claims nothing                       */
+#define MOVBA_ADV_LOST_CLAIM 18   /* an in-bounds feature at a lower position reached the same macroblock first (:306)         */
+#define MOVBA_ADV_FAR        19   /* arrived and won, but dist > 40 (:311); the macroblock stays found                         */
+
+typedef struct {
+    int32_t n_frames, pad;          /* 0 .. MOVBA_MAX_EXPRESS_IMAGES; frames are independent                                */
+    const uint8_t *const *image;    /* n_frames pointers to the frame's 8-bit grey pixels; may be NULL for a frame without
+                                       previous features, macroblocks and lattice.  The PREVIOUS frame has the same size: the
+                                       reference tests :306, :388, :429 against _prev_frame->imageCols/Rows and then reads
+                                       imGrey, which only makes sense for one size                                          */
+    const int32_t *rows, *cols, *stride, *threshold;   /* n_frames each, as movba_express_desc                              */
+    const uint8_t *force_grid;      /* n_frames: _smv->coverageArea < mCoverageThreshold (:418), evaluated by the caller    */
+    const int32_t *first_id;        /* n_frames: mCurrentId on entry, >= 0                                                  */
+    const int32_t *prev_ptr;        /* n_frames + 1, ascending, [0] = 0: the previous features of frame f, in the caller's
+                                       current mvVF order, are [prev_ptr[f], prev_ptr[f + 1]), at most MOVBA_MAX_ADVANCE_PREV */
+    const float    *prev_pt;        /* n_prev x 2: VideoFeature::pt, finite, |.| <= 2^20                                    */
+    const int32_t  *prev_mb;        /* n_prev x 2: mb.width, mb.height, each 8 or 16                                        */
+    const int32_t  *prev_age;       /* n_prev: 0 .. 2^31 - 2                                                                */
+    const int32_t  *prev_track;     /* n_prev: trackId                                                                      */
+    const uint64_t *prev_desc;      /* n_prev x 4: desc, movba_express's bit order                                          */
+    const uint8_t  *prev_coverage;  /* n_prev: VideoFeature::coverage                                                       */
+    const int32_t  *prev_cand;      /* n_prev x 4: _smv->mvi.at<Vec4i>((int)pt.y, (int)pt.x), gathered by the caller: -1 or an
+                                       index into the frame's motion vectors                                                */
+    const int32_t *mv_ptr;          /* n_frames + 1: the motion vectors of frame f                                          */
+    const float   *mv_pt;           /* n_mv x 2: MotionVector::pt, finite, |.| <= 2^20                                      */
+    const int32_t *mv_dindx;        /* n_mv: -1 or an index into the frame's macroblocks                                    */
+    const int32_t *kp_ptr;          /* n_frames + 1: the macroblocks of frame f                                             */
+    const int32_t *kp_rect;         /* n_kps x 4: _smv->kps[i] as x y w h                                                   */
+    const int32_t *grid_ptr;        /* n_frames + 1, or NULL: nothing is covered.  The range of frame f has exactly
+                                       movba_express_grid(rows[f], cols[f]) entries                                         */
+    const uint8_t *grid_covered;    /* per rect of the lattice, in lattice order: non-zero where mvi(kp.pt.y, kp.pt.x)[0] >= 0
+                                       (:431)                                                                               */
+} movba_advance_desc;   /* 184 bytes */
+
+typedef struct {
+    int32_t  *order;                /* n_prev: order[prev_ptr[f] + i] = the input index, within the frame, at position i    */
+    uint8_t  *fate;                 /* n_prev, by input index: MOVBA_ADV_*                                                  */
+    int32_t  *chosen_mv;            /* n_prev, by input index: indx, -1 for MOVBA_ADV_COVERAGE and MOVBA_ADV_NO_MV          */
+    int32_t  *distance;             /* n_prev, by input index: compute_distance of the final rect; -1 where no final descriptor
+                                       was computed (COVERAGE, NO_MV, REJ_BOUNDS).  A LOST_CLAIM feature has one: the call
+                                       describes the final rect before the claims are settled                               */
+    uint8_t  *kp_found;             /* n_kps: lbFound                                                                       */
+    uint8_t  *kp_code;              /* n_kps: MOVBA_EX_* of DETECT on kp_rect; 0 where kp_found skipped it                  */
+    int32_t  *mov_cnt;              /* n_frames: the features of the new segment                                            */
+    uint8_t  *grid_ran;             /* n_frames: force_grid || mov_cnt < 60                                                 */
+    int32_t  *next_id;              /* n_frames: mCurrentId on exit                                                         */
+    int32_t  *seg_ptr;              /* n_frames x 4 + 1: [4 f] .. [4 f + 3] = where the kept, the new and the grid segment of
+                                       frame f start and where the frame ends ([4 f + 3] = [4 f + 4]); the last = the total */
+    int32_t  *feat_src;             /* capacity each = n_prev + n_kps + n_grid (all frames); kept: position i (qIndx), new:
+                                       the macroblock's index, grid: the lattice index                                      */
+    int32_t  *feat_track;           /* trackId                                                                              */
+    float    *feat_pt;              /* capacity x 2                                                                         */
+    int32_t  *feat_rect;            /* capacity x 4: mb as x y w h                                                          */
+    int32_t  *feat_age;
+    uint64_t *feat_desc;            /* capacity x 4                                                                         */
+    int32_t   status, pad;
+} movba_advance_result; /* 136 bytes */
+
+/* Restated as written, quirks included, per frame.  n = the frame's previous features; R, C = rows, cols.
+ *   Sort     (:249-252) position i = 0 .. n - 1 orders the features by age descending, then desc.count() descending.  std::sort
+ *            leaves ties unspecified; HERE TIES STAND IN ASCENDING INPUT INDEX - the one place where the call is more definite
+ *            than the reference.  The reference sorts mvVF in place and qIndx is a position in the sorted vector: the caller
+ *            reorders its mvVF by `order`.
+ *   Feature  at position i, independent of the others.  coverage != 0: MOVBA_ADV_COVERAGE.  cand[0] == -1: MOVBA_ADV_NO_MV.
+ *            Otherwise indx = cand[0], and if cand[1] >= 0: bestDesc = 256; for j = 0 .. 3, stopping at the first cand[j] ==
+ *            -1: if the rect of cand[j] passes movba_express's bounds test, dist = compute_distance(prev_desc,
+ *            compute_descriptor(rect)), and if dist < bestDesc (strict: ties keep the earlier j) bestDesc = dist, indx =
+ *            cand[j].  If no candidate is in bounds indx stays cand[0].
+ *   Rect     of a vector m: pt = prev_pt + mv_pt[m], one fp32 add per component; x = (int)(pt.x - (float)(w / 2)), y =
+ *            (int)(pt.y - (float)(h / 2)): w / 2 the integer quotient, the subtraction in fp32, the conversion truncating
+ *            toward zero - pt.x - 8 = -0.5 gives x = 0, which passes the bounds test, as in the reference; (w, h) = prev_mb.
+ *   Final    rect = the rect of indx, d = mv_dindx[indx].  Out of bounds: MOVBA_ADV_REJ_BOUNDS, no claim.  Else if d >= 0 the
+ *            feature claims macroblock d.
+ *   Claims   (:306-309) lbFound[d] is set by the lowest position among the in-bounds features whose chosen vector has dindx =
+ *            d; every other such feature: MOVBA_ADV_LOST_CLAIM.  A feature with d = -1 never loses.  The claim comes before
+ *            the distance: a winner with dist > 40 still marks the macroblock found.
+ *   Gate     (:311-332) desc, dist of the final rect.  dist <= 40: MOVBA_ADV_KEPT, a feature with trackId = prev_track, qIndx =
+ *            i, pt (the fp32 sum), mb = the final rect, age = prev_age + 1, the new desc.  Otherwise MOVBA_ADV_FAR.
+ *   New      (:380-416) in macroblock order, skipping lbFound: movba_express's DETECT on kp_rect, its bounds and shape codes
+ *            included.  MOVBA_EX_FEATURE: trackId = ++mCurrentId, qIndx = -1, pt = (x + w / 2, y + h / 2) - (br + tl) * 0.5,
+ *            exact for the two widths that pass - mb = the rect, age = 0.  mov_cnt = their number.
+ *   Grid     (:418-451) if force_grid || mov_cnt < 60: DETECT over the lattice of movba_express_grid; its features, in lattice
+ *            order, where grid_covered == 0: trackId = ++mCurrentId, pt = (x + 8, y + 8), mb = the rect, age = 0, coverage =
+ *            true.
+ *   Ids      next_id = first_id + mov_cnt + the grid features emitted; new-segment ids precede grid-segment ids.
+ * The feature list is dense over the call: frame after frame, per frame kept (position order) | new (macroblock order) | grid
+ * (lattice order); entries behind the total are -1 (integers), NaN (feat_pt) and 0 (feat_desc).
+ * What stays with the caller: _keypoints / dIndx numbering, _vfmap, the LK calls (coverage features come back by fate, in
+ * position order), the relocalisation block, pushing `descriptors`.
+ * A frame's result depends on that frame's data alone, and two calls give the same bits.
+ * Returns MOVBA_ERR_ARG for a NULL handle, descriptor or result; n_frames negative or above MOVBA_MAX_EXPRESS_IMAGES; prev_ptr,
+ * mv_ptr, kp_ptr NULL, or one of them or grid_ptr not ascending from 0; more than MOVBA_MAX_ADVANCE_PREV previous features in a
+ * frame; n_prev + n_kps + n_grid (the wave items, n_grid the lattices' rects) above MOVBA_MAX_EXPRESS_ITEMS; a NULL array that
+ * the counts make necessary, or a NULL result array; prev_mb not 8 or 16; prev_age outside 0 .. 2^31 - 2; prev_cand outside
+ * -1 .. n_mv - 1 or mv_dindx outside -1 .. n_kps - 1 (the frame's counts); a prev_pt or mv_pt that is not finite or above 2^20
+ * in magnitude; a grid_covered range whose length is not the lattice's; first_id negative or first_id + n_kps + n_grid above
+ * INT32_MAX; and the image conditions of movba_express (a NULL image for a frame that has items).  MOVBA_ERR_HIP as elsewhere.
+ * Every argument is checked before anything is queued, and on a non-zero status nothing is written except `status`.
+ * n_frames == 0: MOVBA_OK and nothing else written.
+ * One packed copy to the device, four launches - k_adv_sort (a workgroup per frame), k_adv_blocks (a wavefront per previous
+ * feature, macroblock and lattice rect), k_adv_resolve (a workgroup per frame) and k_adv_emit - and one synchronisation; result
+ * arrays that lie in movba_host_alloc memory are written by the kernels themselves.  May share a handle with an uploaded or
+ * solved window, waiting for the window's arrays before it reuses the staging buffer: the window, its results, its marginals
+ * and later runs stay as they were. */
+int  movba_advance(movba_handle *h, const movba_advance_desc *desc, movba_advance_result *res);
 
 #ifdef __cplusplus
 }

@@ -1,7 +1,7 @@
 // Device view + launch wrapper of movba_express (express.hip; host side: express.cpp), and the steps of one item that have a
 // serial meaning - the two tests that keep a rectangle from being read, the centre with its swapped offsets, the wrapped
 // bounds, the diagonals, the descriptor's bit order, the vote state machine - as plain C++ (what k_express calls from its lanes,
-// and what a host build runs item by item: ex_item, ex_counts): the EXPRESS code of EXPRESS.h:79-192 as include/movba.h
+// and what a host build runs item by item: ex_block, ex_item, ex_counts): the EXPRESS code of EXPRESS.h:79-192 as include/movba.h
 // restates it.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -144,7 +144,38 @@ __host__ __device__ inline void ex_write(const ExDev &d, int32_t k, int code, co
     }
 }
 
-// One item on one thread, the steps in the kernel's order.  -> the pass that succeeded (ex_votes) for a feature, else 0
+// One block that passed ex_reject on one thread, the steps in the kernel's order: blk = its first pixel, `cols` bytes from row to
+// row.  -> the code, the descriptor where the code has one (else zeros), *pass = the pass that succeeded (ex_votes) or 0
+inline int ex_block(const uint8_t *blk, int32_t cols, int32_t w, int32_t h, int threshold, int mode, uint64_t desc[4], int *pass)
+{
+    const int center = ex_center(blk, cols, w, h), low = ex_low(center, threshold), high = ex_high(center, threshold);
+    uint64_t t[4] = { 0, 0, 0, 0 }, s[4] = { 0, 0, 0, 0 };
+    int code;
+    desc[0] = desc[1] = desc[2] = desc[3] = 0;
+    *pass = 0;
+    for (int y = 0; y < h; ++y)
+        for (int x = 0; x < w; ++x) {
+            const int p = y * w + x;
+            if (ex_outside(low, high, blk[(size_t)y * cols + x])) t[p >> 6] |= 1ull << (p & 63);
+            if (ex_outside(low, high, blk[(size_t)y * cols + x + 1])) s[p >> 6] |= 1ull << (p & 63);
+        }
+    if (mode == MOVBA_EX_DESCRIBE) code = MOVBA_EX_DESCRIBED;
+    else if (ex_popc256(s) < ex_precheck(w, h)) code = MOVBA_EX_REJ_FLAT;
+    else {
+        *pass = ex_votes(w, h, [&](int ps, int i, int *win, int *len) {
+            uint64_t m[4];
+            ex_diagonal(w, h, ps, i, m);
+            *len = ex_popc256(m);
+            m[0] &= t[0]; m[1] &= t[1]; m[2] &= t[2]; m[3] &= t[3];
+            *win = ex_popc256(m);
+        });
+        code = *pass ? MOVBA_EX_FEATURE : MOVBA_EX_REJ_NO_EDGE;
+    }
+    if (code == MOVBA_EX_FEATURE || code == MOVBA_EX_DESCRIBED) ex_descriptor(s, w, h, desc);
+    return code;
+}
+
+// One item on one thread.  -> the pass that succeeded (ex_votes) for a feature, else 0
 inline int ex_item(const ExDev &d, int32_t k)
 {
     const int32_t x0 = d.item_rect[4 * (size_t)k], y0 = d.item_rect[4 * (size_t)k + 1], w = d.item_rect[4 * (size_t)k + 2], h = d.item_rect[4 * (size_t)k + 3];
@@ -152,32 +183,8 @@ inline int ex_item(const ExDev &d, int32_t k)
     uint64_t desc[4] = { 0, 0, 0, 0 };
     uint64_t *out = d.desc + 4 * (size_t)k;
     int code = ex_reject(x0, y0, w, h, d.rows[im], cols), pass = 0;
-    bool have = false;
-    if (!code) {
-        const uint8_t *blk = d.pixels + d.img_off[im] + (size_t)y0 * cols + x0;
-        const int center = ex_center(blk, cols, w, h), low = ex_low(center, d.threshold[im]), high = ex_high(center, d.threshold[im]);
-        uint64_t t[4] = { 0, 0, 0, 0 }, s[4] = { 0, 0, 0, 0 };
-        for (int y = 0; y < h; ++y)
-            for (int x = 0; x < w; ++x) {
-                const int p = y * w + x;
-                if (ex_outside(low, high, blk[(size_t)y * cols + x])) t[p >> 6] |= 1ull << (p & 63);
-                if (ex_outside(low, high, blk[(size_t)y * cols + x + 1])) s[p >> 6] |= 1ull << (p & 63);
-            }
-        if (d.item_mode[k] == MOVBA_EX_DESCRIBE) code = MOVBA_EX_DESCRIBED;
-        else if (ex_popc256(s) < ex_precheck(w, h)) code = MOVBA_EX_REJ_FLAT;
-        else {
-            pass = ex_votes(w, h, [&](int ps, int i, int *win, int *len) {
-                uint64_t m[4];
-                ex_diagonal(w, h, ps, i, m);
-                *len = ex_popc256(m);
-                m[0] &= t[0]; m[1] &= t[1]; m[2] &= t[2]; m[3] &= t[3];
-                *win = ex_popc256(m);
-            });
-            code = pass ? MOVBA_EX_FEATURE : MOVBA_EX_REJ_NO_EDGE;
-        }
-        have = code == MOVBA_EX_FEATURE || code == MOVBA_EX_DESCRIBED;
-        if (have) ex_descriptor(s, w, h, desc);
-    }
+    if (!code) code = ex_block(d.pixels + d.img_off[im] + (size_t)y0 * cols + x0, cols, w, h, d.threshold[im], d.item_mode[k], desc, &pass);
+    const bool have = code == MOVBA_EX_FEATURE || code == MOVBA_EX_DESCRIBED;
     out[0] = desc[0]; out[1] = desc[1]; out[2] = desc[2]; out[3] = desc[3];
     ex_write(d, k, code, desc, have);
     if (code == MOVBA_EX_FEATURE) d.features[im] += 1;

@@ -27,6 +27,7 @@ _d = C.POINTER(C.c_double)
 _i = C.POINTER(C.c_int32)
 _u = C.POINTER(C.c_uint8)
 _q = C.POINTER(C.c_uint64)
+_f = C.POINTER(C.c_float)
 
 
 class MovbaError(RuntimeError):
@@ -190,6 +191,33 @@ class ExpressResult(C.Structure):
                 ("pad", C.c_int32)]
 
 
+class AdvanceDesc(C.Structure):
+    _fields_ = [("n_frames", C.c_int32), ("pad", C.c_int32), ("image", C.POINTER(C.c_void_p)), ("rows", _i), ("cols", _i),
+                ("stride", _i), ("threshold", _i), ("force_grid", _u), ("first_id", _i), ("prev_ptr", _i), ("prev_pt", _f),
+                ("prev_mb", _i), ("prev_age", _i), ("prev_track", _i), ("prev_desc", _q), ("prev_coverage", _u), ("prev_cand", _i),
+                ("mv_ptr", _i), ("mv_pt", _f), ("mv_dindx", _i), ("kp_ptr", _i), ("kp_rect", _i), ("grid_ptr", _i),
+                ("grid_covered", _u)]
+
+
+class AdvanceResult(C.Structure):
+    _fields_ = [("order", _i), ("fate", _u), ("chosen_mv", _i), ("distance", _i), ("kp_found", _u), ("kp_code", _u),
+                ("mov_cnt", _i), ("grid_ran", _u), ("next_id", _i), ("seg_ptr", _i), ("feat_src", _i), ("feat_track", _i),
+                ("feat_pt", _f), ("feat_rect", _i), ("feat_age", _i), ("feat_desc", _q), ("status", C.c_int32), ("pad", C.c_int32)]
+
+
+# movba_advance_result::fate (MOVBA_ADV_*)
+ADV_KEPT, ADV_COVERAGE = 1, 2
+ADV_NO_MV, ADV_REJ_BOUNDS, ADV_LOST_CLAIM, ADV_FAR = range(16, 20)
+MAX_ADVANCE_PREV = 16384
+# (key, dtype, width, which count it is sized by) of movba_advance_result
+ADVANCE_ARRAYS = (("order", np.int32, 1, "prev"), ("fate", np.uint8, 1, "prev"), ("chosen_mv", np.int32, 1, "prev"),
+                  ("distance", np.int32, 1, "prev"), ("kp_found", np.uint8, 1, "kps"), ("kp_code", np.uint8, 1, "kps"),
+                  ("mov_cnt", np.int32, 1, "frames"), ("grid_ran", np.uint8, 1, "frames"), ("next_id", np.int32, 1, "frames"),
+                  ("seg_ptr", np.int32, 1, "seg"), ("feat_src", np.int32, 1, "cap"), ("feat_track", np.int32, 1, "cap"),
+                  ("feat_pt", np.float32, 2, "cap"), ("feat_rect", np.int32, 4, "cap"), ("feat_age", np.int32, 1, "cap"),
+                  ("feat_desc", np.uint64, 4, "cap"))
+ADVANCE_PREV = (("prev_pt", np.float32, 2), ("prev_mb", np.int32, 2), ("prev_age", np.int32, 1), ("prev_track", np.int32, 1),
+                ("prev_desc", np.uint64, 4), ("prev_coverage", np.uint8, 1), ("prev_cand", np.int32, 4))
 # movba_express_desc::item_mode and movba_express_result::code (MOVBA_EX_*)
 EX_DETECT, EX_DESCRIBE = 0, 1
 EX_FEATURE, EX_DESCRIBED = 1, 2
@@ -242,7 +270,7 @@ EXPORTS = ["movba_version", "movba_status_string", "movba_create", "movba_destro
            "movba_host_alloc", "movba_host_free", "movba_dense_plan_probe", "movba_pose_opt_batch", "movba_lba_marginals", "movba_triangulate",
            "movba_two_view", "movba_two_view_samples", "movba_two_view_lo", "movba_init_map", "movba_view_points",
            "movba_point_normals", "movba_lba_point_normals", "movba_covisibility", "movba_track_match", "movba_express",
-           "movba_express_grid"]
+           "movba_express_grid", "movba_advance"]
 
 _libs = {False: None, True: None}
 
@@ -310,6 +338,7 @@ def lib(hooks: bool = False):
         L.movba_track_match.argtypes = [C.c_void_p, C.POINTER(TrackDesc), C.POINTER(TrackResult)]
         L.movba_express.argtypes = [C.c_void_p, C.POINTER(ExpressDesc), C.POINTER(ExpressResult)]
         L.movba_express_grid.argtypes = [C.c_int32, C.c_int32, _i, C.c_int32]
+        L.movba_advance.argtypes = [C.c_void_p, C.POINTER(AdvanceDesc), C.POINTER(AdvanceResult)]
         L.movba_host_alloc.argtypes = [C.c_size_t]
         L.movba_host_alloc.restype = C.c_void_p
         L.movba_dense_plan_probe.argtypes = [C.c_int32, C.c_int32, C.c_int32, _i, _i, C.c_int32, _i, C.c_int32]
@@ -756,6 +785,76 @@ def express_result(n_items, n_images, alloc=np.zeros, distance=True):
     return r, keep
 
 
+def lattice_size(rows: int, cols: int) -> int:
+    """the number of rects of movba_express_grid(rows, cols)"""
+    return ((rows - 1) // 16) * ((cols - 1) // 16) if rows > 16 and cols > 16 else 0
+
+
+def advance_desc(frames):
+    """frames: one dict per frame with image (2-D uint8, any row stride; None for a frame without items), threshold, force_grid,
+    first_id, prev_pt (n, 2), prev_mb (n, 2), prev_age, prev_track (n,), prev_desc (n, 4) uint64, prev_coverage (n,), prev_cand
+    (n, 4), mv_pt (m, 2), mv_dindx (m,), kp_rect (k, 4) and grid_covered (one entry per lattice rect, or None: nothing is covered;
+    when every frame says None, grid_ptr goes as NULL) -> (movba_advance_desc, the arrays it points into).  keep["n_grid"] is the
+    number of lattice rects of all frames."""
+    nf = len(frames)
+    keep = dict(images=[], rows=np.ones(nf, np.int32), cols=np.ones(nf, np.int32), stride=np.ones(nf, np.int32),
+                threshold=np.array([fr["threshold"] for fr in frames], np.int32).reshape(nf),
+                force_grid=np.array([bool(fr["force_grid"]) for fr in frames], np.uint8).reshape(nf),
+                first_id=np.array([fr["first_id"] for fr in frames], np.int32).reshape(nf), image=(C.c_void_p * max(nf, 1))())
+    lattice = []
+    for i, fr in enumerate(frames):
+        im = fr["image"]
+        if im is not None:
+            if im.dtype != np.uint8 or im.ndim != 2 or (im.shape[1] > 1 and im.strides[1] != 1):
+                raise ValueError("advance_desc: an image is a 2-D uint8 array whose rows are contiguous")
+            keep["images"].append(im)
+            keep["image"][i] = im.ctypes.data
+            keep["rows"][i], keep["cols"][i] = im.shape
+            keep["stride"][i] = im.strides[0] if im.shape[0] > 1 else im.shape[1]
+        lattice.append(lattice_size(int(keep["rows"][i]), int(keep["cols"][i])))
+    keep["n_grid"] = int(sum(lattice))
+
+    def cat(key, dtype, width):
+        parts = [np.asarray(fr[key], dtype).reshape((-1, width) if width > 1 else (-1,)) for fr in frames]
+        ptr = np.concatenate([[0], np.cumsum([len(a) for a in parts])]).astype(np.int32)
+        return np.ascontiguousarray(np.concatenate(parts) if parts else np.zeros((0, width) if width > 1 else (0,)), dtype), ptr
+
+    d = AdvanceDesc()
+    d.n_frames = nf
+    d.image = C.cast(keep["image"], C.POINTER(C.c_void_p))
+    for key, dtype, width in ADVANCE_PREV:
+        keep[key], ptr = cat(key, dtype, width)
+        if "prev_ptr" in keep and not np.array_equal(ptr, keep["prev_ptr"]):
+            raise ValueError("advance_desc: the prev_ arrays of a frame have one row per previous feature")
+        keep["prev_ptr"] = ptr
+    keep["mv_pt"], keep["mv_ptr"] = cat("mv_pt", np.float32, 2)
+    keep["mv_dindx"], ptr = cat("mv_dindx", np.int32, 1)
+    if not np.array_equal(ptr, keep["mv_ptr"]):
+        raise ValueError("advance_desc: mv_pt and mv_dindx have one row per motion vector")
+    keep["kp_rect"], keep["kp_ptr"] = cat("kp_rect", np.int32, 4)
+    if any(fr.get("grid_covered") is not None for fr in frames):
+        parts = [np.zeros(n, np.uint8) if fr.get("grid_covered") is None else np.asarray(fr["grid_covered"]).astype(bool).astype(np.uint8).reshape(-1)
+                 for fr, n in zip(frames, lattice)]
+        keep["grid_covered"] = np.ascontiguousarray(np.concatenate(parts), np.uint8)
+        keep["grid_ptr"] = np.concatenate([[0], np.cumsum([len(a) for a in parts])]).astype(np.int32)
+    types = {np.dtype(np.int32): _i, np.dtype(np.uint8): _u, np.dtype(np.float32): _f, np.dtype(np.uint64): _q}
+    for key, value in keep.items():
+        if isinstance(value, np.ndarray):
+            setattr(d, key, _p(value, types[value.dtype]))
+    return d, keep
+
+
+def advance_result(n_frames, n_prev, n_kps, n_grid, alloc=np.zeros):
+    """-> (movba_advance_result with its output arrays, the arrays it points into)"""
+    size = dict(prev=n_prev, kps=n_kps, frames=n_frames, seg=4 * n_frames + 1, cap=n_prev + n_kps + n_grid)
+    types = {np.int32: _i, np.uint8: _u, np.float32: _f, np.uint64: _q}
+    keep, r = {}, AdvanceResult()
+    for key, dtype, width, which in ADVANCE_ARRAYS:
+        keep[key] = alloc((size[which], width) if width > 1 else (size[which],), dtype)
+        setattr(r, key, _p(keep[key], types[dtype]))
+    return r, keep
+
+
 def run_batch(solvers) -> int:
     """movba_lba_run_batch over the resident windows of `solvers` (created on one stream); download each as usual."""
     arr = (C.c_void_p * len(solvers))(*[s._h for s in solvers])
@@ -1179,6 +1278,20 @@ class Solver:
         if rc < 0:
             raise MovbaError(f"movba_express: {status_string(rc)}")
         out.update(status=rc, item_ptr=keep["item_ptr"])
+        return out
+
+    def advance(self, frames, pinned=False) -> dict:
+        """movba_advance (the inter-frame walk of MOVExtractor: sort, vector choice, claims, gate, new macroblocks, grid, track
+        ids): frames as advance_desc -> dict(status, order, fate, chosen_mv, distance (n_prev,), kp_found, kp_code (n_kps,),
+        mov_cnt, grid_ran, next_id (n_frames,), seg_ptr (4 n_frames + 1,), feat_src, feat_track, feat_pt, feat_rect, feat_age,
+        feat_desc (capacity rows, padded behind seg_ptr[-1]), prev_ptr, kp_ptr).  pinned: result arrays in movba_host_alloc
+        memory, written by the kernels themselves."""
+        d, keep = advance_desc(frames)
+        r, out = advance_result(d.n_frames, len(keep["prev_age"]), len(keep["kp_rect"]), keep["n_grid"], self._pinned if pinned else np.zeros)
+        rc = self._L.movba_advance(self._h, C.byref(d), C.byref(r))
+        if rc < 0:
+            raise MovbaError(f"movba_advance: {status_string(rc)}")
+        out.update(status=rc, prev_ptr=keep["prev_ptr"], kp_ptr=keep["kp_ptr"])
         return out
 
     def lba_point_normals(self, ref_pose, ref_level, scale_factors, outlier=None, pinned=False) -> dict:
