@@ -1199,6 +1199,88 @@ typedef struct {
  * and later runs stay as they were. */
 int  movba_advance(movba_handle *h, const movba_advance_desc *desc, movba_advance_result *res);
 
+/* The decoder's motion-vector image for many frames (streams) per call: the loop of VideoDecoder::NextImage over a frame's
+ * AVMotionVector side data (VideoDecoder.cc:198-351) - the skip of records whose destination block leaves the frame, _smv->kps
+ * and _smv->mvs, the source blocks painted into the CV_32SC4 image _smv->mvi, coverageArea - and the only reads MOVExtractor
+ * makes of that image: at the previous features (MOVExtractor.cc:265-295) and at the lattice centres (:431).  It goes from
+ * the records and the query points to movba_advance's input arrays: the image (16 bytes per pixel, cleared and painted per
+ * frame) is never formed.  The P-frame path with one reference frame: every record has ref == 0 and source < 0, what the
+ * reference's encoder line (ffmpeg.txt: bframes=0:ref=1) produces.  Block sizes are 4, 8 or 16, so every half-size is an
+ * integer and the reference's float arithmetic is exact in integers; every area is a multiple of 16, so its fp32 running sum
+ * is exact up to 2^28.  The result is exact. */
+typedef struct {
+    int32_t n_frames, pad;          /* 0 .. MOVBA_MAX_EXPRESS_IMAGES; frames are independent                                */
+    const int32_t *rows, *cols;     /* n_frames each: height and width, 1 .. 32767                                          */
+    const double  *coverage_threshold;  /* n_frames: mCoverageThreshold, finite                                             */
+    const uint8_t *want_grid;       /* n_frames: non-zero also queries the lattice of movba_express_grid(rows, cols)        */
+    const int32_t *rec_ptr;         /* n_frames + 1, ascending, [0] = 0: the records of frame f, in side-data order, are
+                                       [rec_ptr[f], rec_ptr[f + 1]), at most 2^20 of them                                   */
+    const int16_t *src_x, *src_y, *dst_x, *dst_y;  /* n_records each: AVMotionVector's fields of the same names             */
+    const uint8_t *w, *h;           /* n_records each: 4, 8 or 16                                                           */
+    const int32_t *source, *ref;    /* n_records each: source < 0 and ref == 0; checked, not sent to the device             */
+    const int32_t *q_ptr;           /* n_frames + 1, ascending, [0] = 0: the point queries of frame f                       */
+    const float   *q_pt;            /* n_q x 2: what movba_advance takes as prev_pt; finite, |.| <= 2^20.  The queried pixel
+                                       is ((int)pt.x, (int)pt.y), truncating toward zero as the reference's cast does       */
+} movba_mv_raster_desc;   /* 128 bytes */
+
+typedef struct {
+    int32_t *kept_ptr;              /* n_frames + 1: the kept records of frame f are rows [kept_ptr[f], kept_ptr[f + 1]) of
+                                       kp_rect, mv_pt and mv_dindx: movba_advance's mv_ptr AND kp_ptr                       */
+    int32_t *kp_rect;               /* capacity n_records x 4: _smv->kps as x y w h; behind kept_ptr[n_frames]: -1          */
+    float   *mv_pt;                 /* capacity n_records x 2: MotionVector::pt; behind the total: NaN                      */
+    int32_t *mv_dindx;              /* capacity n_records: MotionVector::dIndx, the index within the frame.  On this path kps
+                                       and mvs are pushed together, so mv_dindx[kept_ptr[f] + m] = m; behind the total: -1  */
+    int32_t *rec_kept;              /* n_records: the index m of the record among its frame's kept records, or -1           */
+    int32_t *cand;                  /* n_q x 4: mvi.at<Vec4i>((int)pt.y, (int)pt.x): -1 or an index m into the frame's kept
+                                       records: movba_advance's prev_cand                                                   */
+    int32_t *grid_ptr;              /* n_frames + 1: the lattice rects of frame f, movba_express_grid(rows[f], cols[f]) of
+                                       them for every frame: movba_advance's grid_ptr                                       */
+    uint8_t *grid_covered;          /* per lattice rect (x, y, 16, 16), in lattice order: 1 where mvi(y + 8, x + 8)[0] >= 0,
+                                       else 0; 0 throughout a frame whose want_grid is 0                                    */
+    int32_t *cover_px;              /* n_frames: the sum of w * h over the kept records                                     */
+    double  *coverage_area;         /* n_frames: _smv->coverageArea                                                         */
+    uint8_t *force_grid;            /* n_frames: coverage_area < coverage_threshold: movba_advance's force_grid             */
+    int32_t  status, pad;
+} movba_mv_raster_result; /* 96 bytes */
+
+/* Restated as written, quirks included, per frame.  W = cols, H = rows; records i in order.
+ *   Keep     (:215-253) hx = w / 2, hy = h / 2.  The record is skipped if dst_x + hx >= W or dst_y + hy >= H.  There is no test
+ *            on the low side: the rect is (max(dst_x - hx, 0), max(dst_y - hy, 0), w, h) and keeps its full size after the
+ *            clamp.  Kept records are numbered densely m = 0, 1, ... in record order; kps[m] and mvs[m] are pushed together,
+ *            so mv_dindx[m] = m.  mv_pt[m] = ((float)(dst_x - src_x), (float)(dst_y - src_y)).
+ *   Coverage (:347-350) cover_px = the sum of w * h over the kept records; coverage_area = (double)cover_px / (double)(W * H);
+ *            force_grid = coverage_area < coverage_threshold, a strict comparison as at MOVExtractor.cc:418.
+ *   Extent   (:291-306) of kept record m: x0 = max(src_x - hx, 0), x1 = min(src_x + hx, W - 1), y0 = max(src_y - hy, 0), y1 =
+ *            min(src_y + hy, H - 1), both ends inclusive: an unclipped block paints (w + 1) x (h + 1) pixels, as the
+ *            reference's <= loops do.  The extent is empty if x0 > x1 or y0 > y1 - a source wholly left of, above, right of or
+ *            below the frame - and still uses up its index m.
+ *   Slots    (:330-345) of a pixel: with m_0 < m_1 < ... < m_(k-1) the kept records whose extent contains it, cand = (m_0,
+ *            m_1, m_2, m_(k-1) if k >= 4 else -1), -1 for the missing ones: the first three records to reach a pixel take
+ *            slots 0 .. 2 and every later one overwrites slot 3.  A function of the set alone.
+ *   Queries  cand for every point query; grid_covered = cand[0] >= 0 at pixel (x + 8, y + 8) of lattice rect (x, y, 16, 16)
+ *            where want_grid is set.  A query pixel outside the image gives four -1: the reference reads outside its matrix
+ *            there - the one place where the call is more definite than the reference.
+ * kept_ptr, kp_rect, mv_pt, mv_dindx, cand, grid_ptr, grid_covered and force_grid go into movba_advance_desc unchanged (kept_ptr
+ * as mv_ptr and kp_ptr, cand as prev_cand).
+ * What stays with the caller: the decoder and its queue, records with ref > 0 (they write into other frames of the queue),
+ * records with source > 0 (B-frames: bmap, which nothing reads), the images.
+ * A frame's result depends on that frame's data alone, and two calls give the same bits.
+ * Returns MOVBA_ERR_ARG for a NULL handle, descriptor or result; n_frames negative or above MOVBA_MAX_EXPRESS_IMAGES; rec_ptr or
+ * q_ptr NULL or not ascending from 0; more than 2^20 records in a frame; n_records + n_q + n_grid (the lattices' rects of all
+ * frames) above MOVBA_MAX_EXPRESS_ITEMS; a NULL array that the counts make necessary (rows, cols, coverage_threshold, want_grid
+ * always), or a NULL result array; rows or cols outside 1 .. 32767, or a sum of rows * cols above 2^28; w or h outside {4, 8,
+ * 16}; ref != 0 or source >= 0; a q_pt that is not finite or above 2^20 in magnitude; a coverage_threshold that is not finite.
+ * MOVBA_ERR_HIP as elsewhere.  Every argument is checked before anything is queued, and on a non-zero status nothing is written
+ * except `status`.  n_frames == 0: MOVBA_OK and nothing else written.
+ * One packed copy to the device, five launches - k_mvr_count and k_mvr_keep (a workgroup per chunk of 1024 records: keep flags,
+ * the dense index from the counts of the chunks before, records per 16 x 16 tile), k_mvr_offsets (one workgroup: kept_ptr,
+ * coverage, tile offsets), k_mvr_fill (a thread per kept record: its rows, its entries in at most 2 x 2 tiles' lists) and
+ * k_mvr_query (a thread per query: its tile's list) - and
+ * one synchronisation; result arrays that lie in movba_host_alloc memory are written by the kernels themselves.  May share a
+ * handle with an uploaded or solved window, waiting for the window's arrays before it reuses the staging buffer: the window,
+ * its results, its marginals and later runs stay as they were. */
+int  movba_mv_raster(movba_handle *h, const movba_mv_raster_desc *desc, movba_mv_raster_result *res);
+
 #ifdef __cplusplus
 }
 #endif

@@ -28,6 +28,7 @@ _i = C.POINTER(C.c_int32)
 _u = C.POINTER(C.c_uint8)
 _q = C.POINTER(C.c_uint64)
 _f = C.POINTER(C.c_float)
+_h = C.POINTER(C.c_int16)
 
 
 class MovbaError(RuntimeError):
@@ -205,6 +206,27 @@ class AdvanceResult(C.Structure):
                 ("feat_pt", _f), ("feat_rect", _i), ("feat_age", _i), ("feat_desc", _q), ("status", C.c_int32), ("pad", C.c_int32)]
 
 
+class MvRasterDesc(C.Structure):
+    _fields_ = [("n_frames", C.c_int32), ("pad", C.c_int32), ("rows", _i), ("cols", _i), ("coverage_threshold", _d), ("want_grid", _u),
+                ("rec_ptr", _i), ("src_x", _h), ("src_y", _h), ("dst_x", _h), ("dst_y", _h), ("w", _u), ("h", _u), ("source", _i),
+                ("ref", _i), ("q_ptr", _i), ("q_pt", _f)]
+
+
+class MvRasterResult(C.Structure):
+    _fields_ = [("kept_ptr", _i), ("kp_rect", _i), ("mv_pt", _f), ("mv_dindx", _i), ("rec_kept", _i), ("cand", _i), ("grid_ptr", _i),
+                ("grid_covered", _u), ("cover_px", _i), ("coverage_area", _d), ("force_grid", _u), ("status", C.c_int32),
+                ("pad", C.c_int32)]
+
+
+# (key, dtype, width, which count it is sized by) of movba_mv_raster_result
+MV_RASTER_ARRAYS = (("kept_ptr", np.int32, 1, "ptr"), ("kp_rect", np.int32, 4, "rec"), ("mv_pt", np.float32, 2, "rec"),
+                    ("mv_dindx", np.int32, 1, "rec"), ("rec_kept", np.int32, 1, "rec"), ("cand", np.int32, 4, "q"),
+                    ("grid_ptr", np.int32, 1, "ptr"), ("grid_covered", np.uint8, 1, "grid"), ("cover_px", np.int32, 1, "frames"),
+                    ("coverage_area", np.float64, 1, "frames"), ("force_grid", np.uint8, 1, "frames"))
+# the per-record fields of movba_mv_raster_desc
+MV_RASTER_RECORD = (("src_x", np.int16), ("src_y", np.int16), ("dst_x", np.int16), ("dst_y", np.int16), ("w", np.uint8), ("h", np.uint8),
+                    ("source", np.int32), ("ref", np.int32))
+MAX_MV_RASTER_RECORDS = 1 << 20
 # movba_advance_result::fate (MOVBA_ADV_*)
 ADV_KEPT, ADV_COVERAGE = 1, 2
 ADV_NO_MV, ADV_REJ_BOUNDS, ADV_LOST_CLAIM, ADV_FAR = range(16, 20)
@@ -270,7 +292,7 @@ EXPORTS = ["movba_version", "movba_status_string", "movba_create", "movba_destro
            "movba_host_alloc", "movba_host_free", "movba_dense_plan_probe", "movba_pose_opt_batch", "movba_lba_marginals", "movba_triangulate",
            "movba_two_view", "movba_two_view_samples", "movba_two_view_lo", "movba_init_map", "movba_view_points",
            "movba_point_normals", "movba_lba_point_normals", "movba_covisibility", "movba_track_match", "movba_express",
-           "movba_express_grid", "movba_advance"]
+           "movba_express_grid", "movba_advance", "movba_mv_raster"]
 
 _libs = {False: None, True: None}
 
@@ -339,6 +361,7 @@ def lib(hooks: bool = False):
         L.movba_express.argtypes = [C.c_void_p, C.POINTER(ExpressDesc), C.POINTER(ExpressResult)]
         L.movba_express_grid.argtypes = [C.c_int32, C.c_int32, _i, C.c_int32]
         L.movba_advance.argtypes = [C.c_void_p, C.POINTER(AdvanceDesc), C.POINTER(AdvanceResult)]
+        L.movba_mv_raster.argtypes = [C.c_void_p, C.POINTER(MvRasterDesc), C.POINTER(MvRasterResult)]
         L.movba_host_alloc.argtypes = [C.c_size_t]
         L.movba_host_alloc.restype = C.c_void_p
         L.movba_dense_plan_probe.argtypes = [C.c_int32, C.c_int32, C.c_int32, _i, _i, C.c_int32, _i, C.c_int32]
@@ -855,6 +878,46 @@ def advance_result(n_frames, n_prev, n_kps, n_grid, alloc=np.zeros):
     return r, keep
 
 
+def mv_raster_desc(frames):
+    """frames: one dict per frame with rows, cols, coverage_threshold, want_grid (optional, 0), records (dict of src_x, src_y, dst_x,
+    dst_y, w, h (n,) and optionally source (-1), ref (0)) and q_pt (k, 2) -> (movba_mv_raster_desc, the arrays it points into).
+    keep["n_grid"] is the number of lattice rects of all frames."""
+    nf = len(frames)
+    keep = dict(rows=np.array([fr["rows"] for fr in frames], np.int32).reshape(nf), cols=np.array([fr["cols"] for fr in frames], np.int32).reshape(nf),
+                coverage_threshold=np.array([fr["coverage_threshold"] for fr in frames], np.float64).reshape(nf),
+                want_grid=np.array([bool(fr.get("want_grid", 0)) for fr in frames], np.uint8).reshape(nf))
+    keep["n_grid"] = int(sum(lattice_size(int(r), int(c)) for r, c in zip(keep["rows"], keep["cols"])))
+    counts = [len(np.asarray(fr["records"]["src_x"]).reshape(-1)) for fr in frames]
+    keep["rec_ptr"] = np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)
+    for key, dtype in MV_RASTER_RECORD:
+        fill = dict(source=-1, ref=0).get(key)
+        parts = [np.asarray(fr["records"][key] if key in fr["records"] else np.full(n, fill), dtype).reshape(-1) for fr, n in zip(frames, counts)]
+        if [len(a) for a in parts] != counts:
+            raise ValueError("mv_raster_desc: the fields of a frame's records have one entry per record")
+        keep[key] = np.ascontiguousarray(np.concatenate(parts) if parts else np.zeros(0), dtype)
+    parts = [np.asarray(fr["q_pt"], np.float32).reshape(-1, 2) for fr in frames]
+    keep["q_ptr"] = np.concatenate([[0], np.cumsum([len(a) for a in parts])]).astype(np.int32)
+    keep["q_pt"] = np.ascontiguousarray(np.concatenate(parts) if parts else np.zeros((0, 2)), np.float32)
+    d = MvRasterDesc()
+    d.n_frames = nf
+    types = {np.dtype(np.int32): _i, np.dtype(np.uint8): _u, np.dtype(np.float32): _f, np.dtype(np.float64): _d, np.dtype(np.int16): _h}
+    for key, value in keep.items():
+        if isinstance(value, np.ndarray):
+            setattr(d, key, _p(value, types[value.dtype]))
+    return d, keep
+
+
+def mv_raster_result(n_frames, n_records, n_q, n_grid, alloc=np.zeros):
+    """-> (movba_mv_raster_result with its output arrays, the arrays it points into)"""
+    size = dict(ptr=n_frames + 1, rec=n_records, q=n_q, grid=n_grid, frames=n_frames)
+    types = {np.int32: _i, np.uint8: _u, np.float32: _f, np.float64: _d}
+    keep, r = {}, MvRasterResult()
+    for key, dtype, width, which in MV_RASTER_ARRAYS:
+        keep[key] = alloc((size[which], width) if width > 1 else (size[which],), dtype)
+        setattr(r, key, _p(keep[key], types[dtype]))
+    return r, keep
+
+
 def run_batch(solvers) -> int:
     """movba_lba_run_batch over the resident windows of `solvers` (created on one stream); download each as usual."""
     arr = (C.c_void_p * len(solvers))(*[s._h for s in solvers])
@@ -1292,6 +1355,21 @@ class Solver:
         if rc < 0:
             raise MovbaError(f"movba_advance: {status_string(rc)}")
         out.update(status=rc, prev_ptr=keep["prev_ptr"], kp_ptr=keep["kp_ptr"])
+        return out
+
+    def mv_raster(self, frames, pinned=False) -> dict:
+        """movba_mv_raster (the decoder's motion-vector image, VideoDecoder::NextImage's loop over the records, read at the query
+        points and never formed): frames as mv_raster_desc -> dict(status, kept_ptr, grid_ptr (n_frames + 1,), kp_rect, mv_pt,
+        mv_dindx (n_records rows, padded behind kept_ptr[-1]), rec_kept (n_records,), cand (n_q, 4), grid_covered (n_grid,),
+        cover_px, coverage_area, force_grid (n_frames,), rec_ptr, q_ptr).  kept_ptr, kp_rect, mv_pt, mv_dindx, cand, grid_covered
+        and force_grid are what advance_desc takes (kept_ptr as mv_ptr and kp_ptr, cand as prev_cand).  pinned: result arrays in
+        movba_host_alloc memory, written by the kernels themselves."""
+        d, keep = mv_raster_desc(frames)
+        r, out = mv_raster_result(d.n_frames, len(keep["src_x"]), len(keep["q_pt"]), keep["n_grid"], self._pinned if pinned else np.zeros)
+        rc = self._L.movba_mv_raster(self._h, C.byref(d), C.byref(r))
+        if rc < 0:
+            raise MovbaError(f"movba_mv_raster: {status_string(rc)}")
+        out.update(status=rc, rec_ptr=keep["rec_ptr"], q_ptr=keep["q_ptr"])
         return out
 
     def lba_point_normals(self, ref_pose, ref_level, scale_factors, outlier=None, pinned=False) -> dict:
