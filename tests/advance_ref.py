@@ -2,7 +2,9 @@
 serial walk in sorted order with a real lbFound list, np.float32 arithmetic and int() truncation, on express_ref's literal block
 functions - and vectorised, written independently - stable argsort, minimum position per macroblock, cumulative sums, on
 express_ref's numpy block function (tests/test_advance_cpu.py holds the two equal on every case); and the committed cases: the
-mixed call, the counts that leave waves partly filled, the bound, the mov_cnt trio.  Everything is integer except one fp32 add
+mixed call, the counts that leave waves partly filled, the bound, the mov_cnt trio, and the three that take the device's own sums
+and scans past their first pass (1 024 frames, the bound's frame behind others, 300 macroblocks and 266 lattice rects).
+Everything is integer except one fp32 add
 and one fp32 subtract per rectangle: every comparison is exact equality.  Helper module: no tests here.
 
 A call is a list of frames as movba.capi.advance_desc takes them: dicts with image, threshold, force_grid, first_id, prev_pt,
@@ -579,6 +581,91 @@ def trio_case():
 @functools.lru_cache(maxsize=None)
 def trio_ref():
     return ref_advance(trio_case())
+
+
+# ---- the cases for what only the device runs: the sums and scans of k_adv_resolve and k_adv_emit ------------------
+
+N_FRAMES = 1024
+FRAMES_ALONE = (0, 85, 86, 255, 256, 1023)
+FRAMES_EMPTY = (0, 1, 500, 501, 502, 1022, 1023)
+
+
+def empty_frame(first_id=0):
+    """a frame without an image and without items"""
+    z = lambda dtype, *shape: np.zeros((0,) + shape, dtype)
+    return dict(image=None, threshold=25, force_grid=0, first_id=first_id, prev_pt=z(np.float32, 2), prev_mb=z(np.int32, 2), prev_age=z(np.int32),
+                prev_track=z(np.int32), prev_desc=z(np.uint64, 4), prev_coverage=z(np.uint8), prev_cand=z(np.int32, 4), mv_pt=z(np.float32, 2),
+                mv_dindx=z(np.int32), kp_rect=z(np.int32, 4), grid_covered=None)
+
+
+@functools.lru_cache(maxsize=None)
+def frames_case():
+    """MOVBA_MAX_EXPRESS_IMAGES frames on images of 17 x 17 up to 33 x 47 with 0 to 4 previous features, 0 to 3 macroblocks and 0 to 3
+    vectors each: k_adv_emit's sum over the 3 x 1 024 counts takes 12 passes of its stride of 256 (frame 85's three counts lie on
+    both sides of the end of the first pass).  FRAMES_EMPTY have no image and no item."""
+    rng = np.random.default_rng(58)
+    frames = []
+    for f in range(N_FRAMES):
+        if f in FRAMES_EMPTY:
+            frames.append(empty_frame(first_id=f))
+            continue
+        low = 1 if f in FRAMES_ALONE else 0
+        image = R.edge_image(rng, int(rng.integers(17, 34)), int(rng.integers(17, 48)))
+        frames.append(random_frame(image, rng, int(rng.integers(low, 5)), n_mv=int(rng.integers(low, 4)), n_kps=int(rng.integers(low, 4)), first_id=7 * f))
+    return frames
+
+
+@functools.lru_cache(maxsize=None)
+def frames_ref():
+    return ref_advance(frames_case())
+
+
+@functools.lru_cache(maxsize=None)
+def behind_case():
+    """the frame of the bound case behind three frames of a few items: the workgroups of k_adv_emit per frame follow the call's
+    AVERAGE frame, so the 16 439 items of the last frame take four passes of the strided loop"""
+    rng = np.random.default_rng(59)
+    tiny = [random_frame(R.edge_image(rng, 17 + k, 20 + k), rng, 2 + k, n_mv=3, n_kps=2, first_id=10 * k) for k in range(3)]
+    return tiny + [bound_case()[0]]
+
+
+@functools.lru_cache(maxsize=None)
+def behind_ref():
+    return ref_advance(behind_case(), literal=False)
+
+
+def emit_chunks(n_items, n_frames):
+    """launch_advance's rule for k_adv_emit's workgroups per frame: min(64, ceil(n_items / n_frames / 256)), the quotient an integer's"""
+    return min(64, max(1, (n_items // n_frames + 255) // 256))
+
+
+def frame_part(res, f):
+    """frame f of a result as the result of a call of that frame alone would hold it, for the per-feature arrays and the feature list"""
+    a, b = int(res["prev_ptr"][f]), int(res["prev_ptr"][f + 1])
+    out = {key: res[key][a:b] for key in PER_PREV}
+    out.update({key: res[key][int(res["seg_ptr"][4 * f]):int(res["seg_ptr"][4 * f + 3])] for key in FEAT})
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def lattice_case():
+    """two frames of 240 x 320 with 300 macroblocks each and the full lattice of 14 x 19 = 266 rects, so that the scans of
+    k_adv_resolve over the macroblocks and over the lattice give every thread two entries: the first with force_grid, a tenth of
+    its lattice covered; the second without, and with enough new features that its lattice is not emitted"""
+    rng = np.random.default_rng(60)
+    frames = []
+    for f in range(2):
+        image = striped_image(rng, 240, 320)
+        image[100:140, 0:320] = 128                                     # (a flat band: rects that are no feature in both ranges)
+        fr = random_frame(image, rng, 60, n_mv=50, n_kps=300, first_id=1000 * f, force_grid=1 - f)
+        fr["grid_covered"] = (rng.random(len(lattice(240, 320))) < 0.1).astype(np.uint8)
+        frames.append(fr)
+    return frames
+
+
+@functools.lru_cache(maxsize=None)
+def lattice_ref():
+    return ref_advance(lattice_case())
 
 
 def read_pixels(fr):

@@ -333,6 +333,31 @@ def mixed_ref(with_refs=True):
     return ref_express(images, items, thr, mixed_refs() if with_refs else None)
 
 
+MANY_IMAGES = 1024
+
+
+@functools.lru_cache(maxsize=None)
+def many_case():
+    """MOVBA_MAX_EXPRESS_IMAGES images of 17 x 17 up to 24 x 40 with 0 to 3 DETECT items each: k_express_counts runs four
+    workgroups.  An image without items is None (a NULL pointer): the first, the last, images 300 to 303 and a sixth of the
+    others.  -> (images, items, threshold)"""
+    rng = np.random.default_rng(20222)
+    images, items = [], []
+    for i in range(MANY_IMAGES):
+        n = 0 if i in (0, MANY_IMAGES - 1, 300, 301, 302, 303) else int(rng.integers(0, 4)) if rng.random() < 0.8 else 0
+        rows_, cols = int(rng.integers(17, 25)), int(rng.integers(17, 41))
+        image = edge_image(rng, rows_, cols)
+        rects = [random_rects(rng, rows_, cols, SHAPES[int(rng.integers(0, 4))], 1) for _ in range(n)]
+        images.append(image if n else None)
+        items.append((np.concatenate(rects) if n else np.zeros((0, 4), np.int32), np.zeros(n, np.int32)))
+    return images, items, 25
+
+
+@functools.lru_cache(maxsize=None)
+def many_ref():
+    return ref_express(*many_case())
+
+
 def read_pixels(rect, cols):
     """the flat indices of every pixel an accepted item reads: the block, the column to its right, and the centre's four"""
     x0, y0, w, h = (int(v) for v in rect)

@@ -3,7 +3,9 @@ loop of VideoDecoder::NextImage with its float half-sizes, its `continue`, its c
 inclusive double loop and the four-way slot fill, the fp32 running sum of the coverage, and then the gathers at the queries - and
 without any painting, written independently - integer keep test, integer extents, and per query the sorted list of the kept
 records that contain the pixel, of which the first three and the last are picked (tests/test_mv_raster_cpu.py holds the two
-equal on every case); and the committed cases.  Everything is exact: every comparison is equality.  Helper module: no tests here.
+equal on every case); a third time with numpy - a keep mask, its cumulative sum, the queries broadcast against the extents -
+for the frame of 66 600 records that the first two cannot walk in seconds (held equal to both on every small case); and the
+committed cases.  Everything is exact: every comparison is equality.  Helper module: no tests here.
 
 A call is a list of frames as movba.capi.mv_raster_desc takes them: dicts with rows, cols, coverage_threshold, want_grid, records
 (a dict of src_x, src_y, dst_x, dst_y, w, h and optionally source, ref) and q_pt."""
@@ -138,19 +140,61 @@ def set_frame(fr):
                 grid_covered=covered, cover_px=cover, coverage_area=area, force_grid=int(area < float(fr["coverage_threshold"])))
 
 
+# ---- (c) with numpy, for the frames too large for (a) and (b) ----------------------------------------------------------------
+
+def slots_of(x0, y0, x1, y1, px, py, chunk=256):
+    """per pixel (px[k], py[k]) the slots from the extents (arrays over the kept records, ascending m): the three smallest m
+    whose extent contains it and, from four on, the largest; `chunk` pixels against all extents at a time -> (len(px), 4)"""
+    out = np.full((len(px), 4), -1, np.int64)
+    if not len(x0):
+        return out
+    for a in range(0, len(px), chunk):
+        x, y = px[a:a + chunk, None], py[a:a + chunk, None]
+        inside = (x0[None, :] <= x) & (x <= x1[None, :]) & (y0[None, :] <= y) & (y <= y1[None, :])
+        count = inside.sum(axis=1)
+        last = inside.shape[1] - 1 - inside[:, ::-1].argmax(axis=1)
+        out[a:a + chunk, 3] = np.where(count >= 4, last, -1)
+        row = np.arange(len(inside))
+        for c in range(3):
+            first = inside.argmax(axis=1)           # (the lowest m; 0 where the row is empty, which `hit` tells apart)
+            hit = inside[row, first]
+            out[a:a + chunk, c] = np.where(hit, first, -1)
+            inside[row, first] = False
+    return out
+
+
+def vector_frame(fr):
+    H, W = int(fr["rows"]), int(fr["cols"])
+    sx, sy, dx, dy, w, h = (np.asarray(fr["records"][k]).reshape(-1).astype(np.int64) for k in FIELDS)
+    keep = ~((dx + w // 2 >= W) | (dy + h // 2 >= H))
+    rec_kept = np.where(keep, np.cumsum(keep) - 1, -1)
+    sx, sy, dx, dy, w, h = (v[keep] for v in (sx, sy, dx, dy, w, h))
+    x0, y0, x1, y1 = np.maximum(sx - w // 2, 0), np.maximum(sy - h // 2, 0), np.minimum(sx + w // 2, W - 1), np.minimum(sy + h // 2, H - 1)
+    cover = int((w * h).sum())
+    area = cover / (W * H)
+    q = np.trunc(np.asarray(fr["q_pt"], np.float32).reshape(-1, 2)).astype(np.int64)
+    cand = slots_of(x0, y0, x1, y1, q[:, 0], q[:, 1])
+    cand[(q[:, 0] < 0) | (q[:, 1] < 0) | (q[:, 0] >= W) | (q[:, 1] >= H)] = -1
+    lat = np.array(lattice(H, W), np.int64).reshape(-1, 4)
+    covered = (slots_of(x0, y0, x1, y1, lat[:, 0] + 8, lat[:, 1] + 8)[:, 0] >= 0) if fr.get("want_grid", 0) else np.zeros(len(lat), bool)
+    return dict(kp_rect=np.stack([np.maximum(dx - w // 2, 0), np.maximum(dy - h // 2, 0), w, h], axis=1), mv_pt=np.stack([dx - sx, dy - sy], axis=1).astype(np.float32),
+                mv_dindx=np.arange(len(w)), rec_kept=rec_kept, cand=cand, grid_covered=covered.astype(np.uint8), cover_px=cover, coverage_area=area,
+                force_grid=int(area < float(fr["coverage_threshold"])))
+
+
 # ---- a whole call ------------------------------------------------------------------------------------------------------------
 
-def ref_mv_raster(frames, literal=True):
-    """-> the fields of Solver.mv_raster's dict"""
-    per = [(literal_frame if literal else set_frame)(fr) for fr in frames]
+def ref_mv_raster(frames, literal=True, vector=False):
+    """-> the fields of Solver.mv_raster's dict; (a) by default, (b) with literal=False, (c) with vector=True"""
+    per = [(vector_frame if vector else literal_frame if literal else set_frame)(fr) for fr in frames]
     n_rec = sum(len(p["rec_kept"]) for p in per)
 
     def ptr(counts):
         return np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)
 
     def cat(key, dtype, width=1):
-        a = np.array([v for p in per for v in p[key]], dtype)
-        return a.reshape(-1, width) if width > 1 else a.reshape(-1)
+        parts = [np.asarray(p[key], dtype).reshape((-1, width) if width > 1 else (-1,)) for p in per]
+        return np.concatenate(parts) if parts else np.zeros((0, width) if width > 1 else (0,), dtype)
 
     out = dict(status=0, kept_ptr=ptr([len(p["kp_rect"]) for p in per]), grid_ptr=ptr([len(p["grid_covered"]) for p in per]),
                rec_kept=cat("rec_kept", np.int32), cand=cat("cand", np.int32, 4), grid_covered=cat("grid_covered", np.uint8),
@@ -344,3 +388,108 @@ def edge_case():
     recs = [(4, 4, 10, 10, 8, 8), (W - 3, 3, 12, 12, 8, 8), (3, H - 3, 12, 12, 8, 8), (2, 2, 14, 14, 16, 16)]
     q = [(-0.5, -0.5), (W, 0), (0, H), (W - 0.5, 0.25), (0.75, H - 0.5), (-1.0, 0), (0, -1.0), (-0.99, -0.99), (W + 5.0, H + 5.0), (-1048576.0, 1048576.0)]
     return [frame(H, W, recs, q)]
+
+
+# ---- the cases for what only the device runs: the scans over chunks, frames and tiles ----------------------------
+
+CHUNKS_SHAPE, CHUNKS_RECORDS, CHUNKS_QUERIES = (528, 544), 66600, 2000
+CHUNKS_BAND = 480               # no source extent reaches a row from here on
+
+
+@functools.lru_cache(maxsize=None)
+def chunks_case():
+    """one frame of 528 x 544 - 33 x 34 = 1 122 tiles, two per thread of the tile scan and none from thread 561 on - with 66 600
+    records: 66 chunks of 1 024, 40 records in the last, so the carry of chunks 64 and 65 sums over two wavefronts.  About 3 % of the
+    records are skipped, the last but one among them; no source reaches the rows from CHUNKS_BAND on, so the tiles there are
+    empty and a query there has no record; 2 000 queries, some outside the frame; the lattice is wanted."""
+    rng = np.random.default_rng(15)
+    rows, cols = CHUNKS_SHAPE
+    n = CHUNKS_RECORDS
+    recs = np.stack([rng.integers(-24, cols + 24, n), rng.integers(-24, CHUNKS_BAND - 10, n), rng.integers(-6, cols + 6, n), rng.integers(-6, rows + 6, n),
+                     rng.choice(SIZES, n), rng.choice(SIZES, n)], axis=1)
+    recs[n - 2] = (100, 100, cols, 100, 8, 8)               # skipped
+    recs[n - 1] = (100, 100, 100, 100, 16, 16)              # kept
+    q = np.stack([rng.uniform(-3, cols + 3, CHUNKS_QUERIES), rng.uniform(-3, rows + 3, CHUNKS_QUERIES)], axis=1)
+    return [frame(rows, cols, recs, q, threshold=19.0, want_grid=1)]
+
+
+@functools.lru_cache(maxsize=None)
+def chunks_ref():
+    return ref_mv_raster(chunks_case(), vector=True)
+
+
+@functools.lru_cache(maxsize=None)
+def chunks_head():
+    """what (a) and (b) say about the part of the chunks case they can walk: the records of the first chunk painted alone (their
+    rows do not depend on what follows them), and every 20th query against the sets of (b) over all records
+    -> (the literal result of the first 1 024 records, the queries taken, their slots)"""
+    fr = chunks_case()[0]
+    first = dict(fr, records={k: v[:1024] for k, v in fr["records"].items()}, q_pt=np.zeros((0, 2), np.float32), want_grid=0)
+    taken = np.arange(0, CHUNKS_QUERIES, 20)
+    _, kept = kept_records(fr)
+    extents = [extent(r, fr["cols"], fr["rows"]) for r in kept]
+    pixels = query_pixels(fr)
+    slots = [slots_at(extents, *pixels[j]) if 0 <= pixels[j][0] < fr["cols"] and 0 <= pixels[j][1] < fr["rows"] else [-1] * 4 for j in taken]
+    return ref_mv_raster([first]), taken, np.array(slots, np.int32)
+
+
+def compare_head(res):
+    """a result of the chunks case against chunks_head"""
+    lit, taken, slots = chunks_head()
+    k = int(lit["kept_ptr"][1])
+    assert 0 < k < 1024 and np.array_equal(res["rec_kept"][:1024], lit["rec_kept"])
+    assert np.array_equal(res["kp_rect"][:k], lit["kp_rect"][:k]) and np.array_equal(res["mv_dindx"][:k], lit["mv_dindx"][:k])
+    assert np.array_equal(res["mv_pt"][:k].view(np.uint32), lit["mv_pt"][:k].view(np.uint32))
+    assert np.array_equal(res["cand"][taken], slots), np.flatnonzero((res["cand"][taken] != slots).any(axis=1))[:8].tolist()
+
+
+MULTIPLES = (1024, 2048, 1025)
+
+
+@functools.lru_cache(maxsize=None)
+def multiples_case():
+    """three frames of 1 024, 2 048 and 1 025 records on 64 x 96 images: a last chunk that is full, and a chunk number at which
+    the frame has exactly no record left.  Every fifth record is skipped; the last record of the first two frames is kept, the
+    last of the third - a chunk of its own - is skipped."""
+    rng = np.random.default_rng(16)
+    frames = []
+    for n in MULTIPLES:
+        recs = random_records(rng, 64, 96, n, margin=10)
+        recs = [(r[0], r[1], 96 if i % 5 == 3 else min(max(r[2], 0), 80), min(max(r[3], 0), 50), r[4], r[5]) for i, r in enumerate(recs)]
+        recs[-1] = (10, 10, 96, 20, 8, 8) if n == 1025 else (10, 10, 20, 20, 16, 16)
+        q = np.stack([rng.uniform(0, 96, 65), rng.uniform(0, 64, 65)], axis=1)
+        frames.append(frame(64, 96, recs, q, threshold=float(rng.uniform(0.2, 30.0)), want_grid=1))
+    return frames
+
+
+@functools.lru_cache(maxsize=None)
+def multiples_ref():
+    return ref_mv_raster(multiples_case())
+
+
+N_FRAMES = 1024
+FRAMES_ALONE = (0, 63, 64, 65, 511, 1023)
+FRAMES_NO_RECORDS = (0, 1, 2, 400, 401, 402, 403, 404, 1021, 1022, 1023)
+FRAMES_NO_QUERIES = (0, 1, 700, 701, 702, 703, 1022, 1023)
+
+
+@functools.lru_cache(maxsize=None)
+def frames_case():
+    """MOVBA_MAX_EXPRESS_IMAGES frames of 16 x 16 up to 40 x 40 with 0 to 5 records and 0 to 3 queries each: the scan over the frames'
+    kept counts takes all 16 wavefronts, the tile scan (more than 1 024 tiles) crosses frames, and the searches over rec_ptr, q_ptr
+    and g_ptr meet runs of equal entries - frames without records (FRAMES_NO_RECORDS), without queries (FRAMES_NO_QUERIES) and,
+    at 16 pixels, without a lattice."""
+    rng = np.random.default_rng(17)
+    frames = []
+    for f in range(N_FRAMES):
+        rows, cols = int(rng.integers(16, 41)), int(rng.integers(16, 41))
+        n = 0 if f in FRAMES_NO_RECORDS else int(rng.integers(1 if f in FRAMES_ALONE else 0, 6))
+        nq = 0 if f in FRAMES_NO_QUERIES else int(rng.integers(1 if f in FRAMES_ALONE else 0, 4))
+        q = np.stack([rng.uniform(-1, cols + 1, nq), rng.uniform(-1, rows + 1, nq)], axis=1)
+        frames.append(frame(rows, cols, random_records(rng, rows, cols, n, margin=8), q, threshold=float(rng.uniform(0.0, 1.0)), want_grid=int(rng.integers(0, 2))))
+    return frames
+
+
+@functools.lru_cache(maxsize=None)
+def frames_ref():
+    return ref_mv_raster(frames_case())

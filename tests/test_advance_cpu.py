@@ -29,6 +29,13 @@ def test_the_two_restatements_agree_on_every_case():
     A.compare(A.ref_advance(A.trio_case(), literal=False), A.trio_ref(), "trio")
     # the bound: the literal walk over the first 500 positions (what lies behind them cannot change them)
     A.compare_head(A.bound_ref())
+    A.compare(A.ref_advance(A.frames_case(), literal=False), A.frames_ref(), "frames")
+    A.compare(A.ref_advance(A.lattice_case(), literal=False), A.lattice_ref(), "lattice")
+    # the bound's frame behind three others: the same walk over its rows, and the three literally
+    A.compare_head(A.frame_part(A.behind_ref(), 3))
+    lit = A.ref_advance(A.behind_case()[:3])
+    for f in range(3):
+        assert A.frame_rows(lit, f) == A.frame_rows(A.behind_ref(), f), f
 
 
 def test_mixed_case_meets_the_input_conditions():
@@ -176,6 +183,68 @@ def test_counts_case_is_what_the_gpu_test_asks_for():
     assert len(A.bound_case()[0]["prev_age"]) == 16384 and A.bound_case()[0]["image"].shape == (64, 96)
 
 
+def _items(fr):
+    return len(fr["prev_age"]) + len(fr["kp_rect"]) + len(A.lattice(*A.shape_of(fr)))
+
+
+def test_frames_behind_and_lattice_cases_are_what_the_gpu_tests_ask_for():
+    """the inputs that take the sums and scans only the device runs - k_adv_emit's sum over the frames' counts and its strided
+    item loop, k_adv_resolve's scans over macroblocks and lattice - past their first pass"""
+    # many frames
+    frames, ref = A.frames_case(), A.frames_ref()
+    assert len(frames) == A.N_FRAMES == 1024 and 3 * 85 == 255                    # (the counts of frame 85 lie on both sides of the first pass of 256)
+    shapes = [fr["image"].shape for fr in frames if fr["image"] is not None]
+    assert all(17 <= r <= 33 and 17 <= c <= 47 for r, c in shapes) and len(set(shapes)) > 200
+    n_prev, n_kp = np.diff(ref["prev_ptr"]), np.diff(ref["kp_ptr"])
+    n_mv = np.array([len(fr["mv_dindx"]) for fr in frames])
+    assert (n_prev.min(), n_prev.max(), n_kp.min(), n_kp.max(), n_mv.min(), n_mv.max()) == (0, 4, 0, 3, 0, 3)
+    for f in A.FRAMES_EMPTY:
+        assert frames[f]["image"] is None and _items(frames[f]) == 0, f
+    assert A.FRAMES_EMPTY[0] == 0 and A.FRAMES_EMPTY[-1] == 1023 and any(0 < f < 1023 for f in A.FRAMES_EMPTY)
+    seg = ref["seg_ptr"][:-1].reshape(1024, 4)
+    for part, name in enumerate(("kept", "new", "grid")):
+        count = seg[:, part + 1] - seg[:, part]
+        assert count[:86].sum() > 0 and count[86:].sum() > 0, name                       # on both sides of frame 86
+        assert all(count[256 * k:256 * (k + 1)].sum() > 0 for k in range(4)), name
+    assert A.FRAMES_ALONE == (0, 85, 86, 255, 256, 1023) and all(_items(frames[f]) >= 3 for f in (85, 86, 255, 256))
+    assert ref["seg_ptr"][-1] < len(ref["feat_src"]) and np.array_equal(ref["seg_ptr"][4::4], seg[1:, 0].tolist() + [ref["seg_ptr"][-1]])
+    # the bound's frame behind three others
+    frames, ref = A.behind_case(), A.behind_ref()
+    assert len(frames) == 4 and frames[3] is A.bound_case()[0] and all(0 < _items(fr) < 30 for fr in frames[:3])
+    n_items = sum(_items(fr) for fr in frames)
+    chunks = A.emit_chunks(n_items, 4)
+    # (not 16: the frame's 16 384 features, 40 macroblocks and 15 lattice rects and the small frames' items over 4 frames make 17
+    # by the launch rule - what matters is that they are far fewer than the 64 the frame gets alone, and the four passes)
+    assert chunks == 17 < A.emit_chunks(_items(frames[3]), 1) == 64
+    assert _items(frames[3]) >= 16384 and -(-_items(frames[3]) // (chunks * 256)) >= 4
+    s = ref["seg_ptr"][12:16]
+    p0 = int(ref["prev_ptr"][3])
+    kept_items = ref["order"][p0 + ref["feat_src"][s[0]:s[1]]]                           # the wave items of the frame's kept features
+    assert s[0] > 0 and set((kept_items // (256 * chunks)).tolist()) == {0, 1, 2, 3}     # rows come from every pass of the loop
+    assert s[2] > s[1] and s[3] > s[2] and (16384 // (256 * chunks)) == 3                # ... the new and the grid features from the last
+    # one 240 x 320 frame, and a second whose lattice is not emitted
+    frames, ref = A.lattice_case(), A.lattice_ref()
+    assert all(fr["image"].shape == (240, 320) and len(fr["kp_rect"]) == 300 for fr in frames)
+    from movba import capi
+    grid = capi.express_grid(240, 320)
+    assert len(grid) == 266 == len(A.lattice(240, 320)) and grid.tolist() == [list(r) for r in A.lattice(240, 320)]
+    assert (300 + 255) // 256 == 2 and (266 + 255) // 256 == 2                           # two entries per thread in both scans
+    assert [fr["force_grid"] for fr in frames] == [1, 0] and ref["grid_ran"].tolist() == [1, 0] and ref["mov_cnt"][1] >= 60
+    seg = ref["seg_ptr"]
+    for f in range(2):
+        new = ref["feat_src"][seg[4 * f + 1]:seg[4 * f + 2]]
+        assert (new < 256).any() and (new >= 256).any() and new.max() < 300, f          # new macroblocks in both ranges
+        code = ref["kp_code"][300 * f:300 * (f + 1)]
+        assert ((code[:256] != R.EX_FEATURE).any() and (code[256:] != R.EX_FEATURE).any()) and ref["kp_found"][300 * f:300 * (f + 1)].any()
+    g = ref["feat_src"][seg[2]:seg[3]]
+    assert (g < 256).any() and (g >= 256).any() and g.max() < 266 and len(g) < 266 - 20     # grid features in both ranges, not all
+    covered = frames[0]["grid_covered"]
+    assert covered[:256].any() and not covered[g].any()
+    assert seg[7] == seg[6] and frames[1]["grid_covered"].sum() < 266                    # nothing of the second frame's lattice
+    would = [R.fast_item(frames[1]["image"], mb, R.EX_DETECT, 25)[0] == R.EX_FEATURE for mb in A.lattice(240, 320)]
+    assert sum(would) > 100                                                              # ... though it has features enough
+
+
 # ---- C-ABI without a device ------------------------------------------------------------------------------------------------
 
 def test_symbol_and_struct_layouts(built_lib, tmp_path):
@@ -297,7 +366,7 @@ def run_adv_main(exe, frames, tmp_path):
     from movba import capi
     d, keep = capi.advance_desc(frames)
     nf, n_prev, n_mv, n_kps, n_grid = len(frames), len(keep["prev_age"]), len(keep["mv_dindx"]), len(keep["kp_rect"]), keep["n_grid"]
-    lat = [len(A.lattice(*fr["image"].shape)) for fr in frames]
+    lat = [len(A.lattice(*A.shape_of(fr))) for fr in frames]
     covered = keep.get("grid_covered", np.zeros(n_grid, np.uint8))
     src, dst = os.path.join(str(tmp_path), "call.bin"), os.path.join(str(tmp_path), "out.bin")
     with open(src, "wb") as f:
@@ -307,7 +376,7 @@ def run_adv_main(exe, frames, tmp_path):
                   keep["prev_track"], keep["prev_cand"], keep["prev_desc"], keep["prev_coverage"], keep["mv_pt"], keep["mv_dindx"], keep["kp_rect"], covered):
             f.write(a.tobytes())
         for fr in frames:
-            f.write(np.ascontiguousarray(fr["image"]).tobytes())
+            f.write(b"\0" if fr["image"] is None else np.ascontiguousarray(fr["image"]).tobytes())     # (None: 1 x 1 in the descriptor, never read)
     r = subprocess.run([exe, src, dst], env=dict(os.environ, **SAN_ENV), capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and "adv_main: ok" in r.stdout and "Sanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-4000:]
     blob = open(dst, "rb").read()
@@ -328,13 +397,17 @@ def run_adv_main(exe, frames, tmp_path):
     return out
 
 
-@pytest.mark.parametrize("case", ["mixed", "counts", "trio"])
+ALONE = dict(counts=(0, 1, 4), frames=A.FRAMES_ALONE, behind=(0, 1, 2))         # the frames run alone too; every frame where nothing is said
+
+
+@pytest.mark.parametrize("case", ["mixed", "counts", "trio", "frames", "behind", "lattice"])
 def test_the_librarys_steps_on_every_case(adv_main, tmp_path, case):
-    frames, ref = dict(mixed=(A.mixed_case()[0], A.mixed_ref), counts=(A.counts_case(), A.counts_ref), trio=(A.trio_case(), A.trio_ref))[case]
+    frames, ref = dict(mixed=(A.mixed_case()[0], A.mixed_ref), counts=(A.counts_case(), A.counts_ref), trio=(A.trio_case(), A.trio_ref),
+                       frames=(A.frames_case(), A.frames_ref), behind=(A.behind_case(), A.behind_ref), lattice=(A.lattice_case(), A.lattice_ref))[case]
     A.compare(run_adv_main(adv_main, frames, tmp_path), ref(), case)
     # every frame alone: its image is the whole pixel buffer, so a read behind it is seen
     for f, fr in enumerate(frames):
-        if case == "counts" and f not in (0, 1, 4):
+        if f not in ALONE.get(case, range(len(frames))):
             continue
         A.compare(run_adv_main(adv_main, [fr], tmp_path), A.ref_advance([fr], literal=False), f"{case}, frame {f} alone")
 

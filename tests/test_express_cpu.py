@@ -32,6 +32,31 @@ def test_the_two_restatements_agree_on_every_case():
     R.compare(fast, R.mixed_ref(), "mixed")
     assert np.array_equal(fast["passes"], R.mixed_ref()["passes"])
     R.compare(R.ref_express(images, items, thr, None, literal=False), R.mixed_ref(False), "mixed, no references")
+    fast = R.ref_express(*R.many_case(), literal=False)
+    R.compare(fast, R.many_ref(), "many")
+    assert np.array_equal(fast["passes"], R.many_ref()["passes"])
+
+
+def test_many_case_is_what_the_gpu_test_asks_for():
+    """what takes k_express_counts to its second, third and fourth workgroup: features in images above 255, 511 and 767"""
+    images, items, thr = R.many_case()
+    ref = R.many_ref()
+    assert len(images) == len(items) == R.MANY_IMAGES == 1024 and thr == 25
+    counts = np.array([len(r) for r, _ in items])
+    assert counts.min() == 0 and counts.max() == 3 and set(counts.tolist()) == {0, 1, 2, 3}
+    assert all((im is None) == (n == 0) for im, n in zip(images, counts))
+    shapes = [im.shape for im in images if im is not None]
+    assert all(17 <= r <= 24 and 17 <= c <= 40 for r, c in shapes) and len(set(shapes)) > 100
+    # images without items first, last and in a run in the middle
+    assert counts[0] == 0 and counts[-1] == 0 and (counts[300:304] == 0).all() and counts[1:300].any() and counts[304:-1].any()
+    assert np.array_equal(np.diff(ref["item_ptr"]), counts)
+    feats = ref["n_features"]
+    assert feats.shape == (1024,) and feats.sum() == (ref["code"] == R.EX_FEATURE).sum()
+    for block in range(4):                  # (one workgroup of k_express_counts per 256 images)
+        part = feats[256 * block:256 * (block + 1)]
+        assert (part > 0).sum() >= 20 and (part == 0).sum() >= 20, block
+    assert feats[256:].any() and feats[512:].any() and feats[768:].any() and set(feats.tolist()) >= {0, 1, 2}
+    assert (feats[counts == 0] == 0).all() and (feats < counts).any()
 
 
 def test_coverage_case_meets_the_input_conditions():
@@ -242,7 +267,7 @@ def run_ex_main(exe, images, items, thresholds, refs, tmp_path):
         if refs is not None:
             f.write(keep["item_ref"].tobytes())
         for im in images:
-            f.write(np.ascontiguousarray(im).tobytes())
+            f.write(b"\0" if im is None else np.ascontiguousarray(im).tobytes())        # (None: 1 x 1 in the descriptor, never read)
     r = subprocess.run([exe, src, dst], env=dict(os.environ, **SAN_ENV), capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and "ex_main: ok" in r.stdout and "Sanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-4000:]
     blob = open(dst, "rb").read()
@@ -273,6 +298,12 @@ def test_the_librarys_steps_on_the_mixed_case(ex_main, tmp_path):
     R.compare(got, R.mixed_ref(), "mixed")
     assert np.array_equal(got["passes"], R.mixed_ref()["passes"])
     R.compare(run_ex_main(ex_main, images, items, thr, None, tmp_path), R.mixed_ref(False), "mixed, no references")
+
+
+def test_the_librarys_steps_on_the_many_case(ex_main, tmp_path):
+    got = run_ex_main(ex_main, *R.many_case(), None, tmp_path)
+    R.compare(got, R.many_ref(), "many")
+    assert np.array_equal(got["passes"], R.many_ref()["passes"])
 
 
 def test_the_librarys_diagonals_are_the_rules(ex_main, tmp_path):

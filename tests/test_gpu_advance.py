@@ -1,6 +1,8 @@
 """movba_advance on the device against the restatements of tests/advance_ref.py, every comparison exact equality: the mixed call
 array by array, padding included; previous-feature counts that leave waves and workgroups partly filled and the sort's padding
-at work; the bound of 16384 features; the mov_cnt trio of 59, 60 and 60 + force_grid; independence of a frame from the other
+at work; the bound of 16384 features; the sizes at which the sums and scans that only the device runs take a second pass - 1 024
+frames, the bound's frame behind three small ones, 300 macroblocks and 266 lattice rects in one frame; the mov_cnt trio of 59,
+60 and 60 + force_grid; independence of a frame from the other
 frames, from how the frames are split over calls and from pixels none of its items read, and what a permutation of a frame's
 features may change; pinned results; a solved window on the same handle left as it was; a refusal and an empty call on a live
 handle.  Every rect the device reads is inside its image by the reference's own test (tests/test_advance_cpu.py holds the
@@ -42,6 +44,40 @@ def test_the_bound_of_previous_features(solver):
     A.compare(got, A.bound_ref(), "bound")
     A.compare_head(got)
     assert len(got["order"]) == capi.MAX_ADVANCE_PREV and sorted(got["order"].tolist()) == list(range(16384))
+
+
+def test_1024_frames_take_the_sum_of_the_emit_over_every_pass(solver):
+    """MOVBA_MAX_EXPRESS_IMAGES frames of 0 to 4 previous features, 0 to 3 macroblocks and 0 to 3 vectors, frames without anything
+    first, last and in the middle: k_adv_emit's sum over the 3 x 1 024 counts, which only the device runs, in 12 passes of its
+    stride.  seg_ptr in full, every array, and six frames alone against their rows."""
+    frames, ref = A.frames_case(), A.frames_ref()
+    got = solver.advance(frames)
+    assert got["status"] == 0 and len(got["seg_ptr"]) == 4 * A.N_FRAMES + 1
+    assert np.array_equal(got["seg_ptr"], ref["seg_ptr"]), np.flatnonzero(got["seg_ptr"] != ref["seg_ptr"])[:8].tolist()
+    A.compare(got, ref, "frames")
+    for f in A.FRAMES_ALONE:
+        assert A.frame_rows(solver.advance([frames[f]]), 0) == A.frame_rows(got, f) == A.frame_rows(ref, f), f
+
+
+def test_the_bound_frame_behind_three_small_ones(solver):
+    """the 16 384 features of the bound case as the last of four frames: k_adv_emit's workgroups per frame follow the average
+    frame, so the frame's items take four passes of the strided loop instead of one"""
+    frames = A.behind_case()
+    got = solver.advance(frames)
+    A.compare(got, A.behind_ref(), "behind")
+    A.compare_head(A.frame_part(got, 3))
+    assert A.frame_rows(got, 3) == A.frame_rows(solver.advance(A.bound_case()), 0)
+
+
+def test_two_macroblocks_and_two_lattice_rects_per_thread(solver):
+    """two frames of 240 x 320 with 300 macroblocks and the lattice of 266 rects: k_adv_resolve's scans over both give a thread
+    two entries.  The first frame emits its lattice (force_grid), the second has 60 new features and more and emits none."""
+    frames, ref = A.lattice_case(), A.lattice_ref()
+    got = solver.advance(frames)
+    A.compare(got, ref, "lattice")
+    assert got["grid_ran"].tolist() == [1, 0] and got["seg_ptr"][3] > got["seg_ptr"][2] and got["seg_ptr"][7] == got["seg_ptr"][6]
+    for f in range(2):
+        assert A.frame_rows(solver.advance([frames[f]]), 0) == A.frame_rows(got, f), f
 
 
 def test_the_mov_cnt_trio(solver):

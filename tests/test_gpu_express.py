@@ -1,5 +1,6 @@
 """movba_express on the device against the literal restatement of tests/express_ref.py, every comparison exact equality: the mixed
-call array by array, item counts that leave workgroups partly filled, the grid of a 240 x 320 frame, independence of an item
+call array by array, 1 024 images (k_express_counts over four workgroups), item counts that leave workgroups partly filled, the
+grid of a 240 x 320 frame, independence of an item
 from everything but its own rect, mode, reference and image (reordered, split over calls, a pixel changed elsewhere), pinned
 results, a solved window on the same handle left as it was, a refusal on a live handle, and the distance against an item's own
 descriptor and its complement.  Every rect handed to the device is inside its image by the reference's own test or carries a
@@ -36,6 +37,20 @@ def test_parity_with_the_restatement_on_a_mixed_call(solver):
     assert solver._L.movba_express(solver._h, C.byref(d), C.byref(r)) == 0 and r.status == 0
     for key in ("code", "desc", "count", "n_features"):
         assert np.array_equal(out[key], R.mixed_ref()[key]), key
+
+
+def test_1024_images_take_the_counts_over_four_workgroups(solver):
+    """MOVBA_MAX_EXPRESS_IMAGES images of 17 x 17 to 24 x 40 with 0 to 3 items each, the ones without items NULL - the first, the
+    last and a run in the middle among them: k_express_counts, which only the device runs, over four workgroups.  n_features
+    in full, and every item's row."""
+    images, items, thr = R.many_case()
+    ref = R.many_ref()
+    got = solver.express(images, items, thr)
+    assert got["status"] == 0 and got["n_features"].shape == (R.MANY_IMAGES,)
+    assert np.array_equal(got["n_features"], ref["n_features"]), np.flatnonzero(got["n_features"] != ref["n_features"])[:8].tolist()
+    R.compare(got, ref, "many")
+    assert got["n_features"][256:512].any() and got["n_features"][512:768].any() and got["n_features"][768:].any()
+    R.compare(solver.express(images, items, thr, pinned=True), ref, "many, pinned")
 
 
 @pytest.mark.parametrize("n", [1, 3, 4, 5, 257])

@@ -1,6 +1,8 @@
 """movba_mv_raster on the device against the restatements of tests/mv_raster_ref.py, every comparison exact equality: the full
 raster of a 48 x 40 frame (and of its transpose) with every clamp among its records; piles of 3, 4, 5 and 70 records on one
-pixel; record and query counts that leave wavefronts partly filled and take the scan's carry over chunk boundaries; the mixed
+pixel; record and query counts that leave wavefronts partly filled and take the scan's carry over chunk boundaries; the sizes
+at which the scans that only the device runs cross a wavefront - 66 chunks in one frame, record counts that are multiples of
+the chunk, 1 024 frames with runs of empty ones; the mixed
 call with an I-frame, a frame without queries and lattice, the padding and frame-by-frame independence; the coverage gate on
 its boundary; queries on and over the edge; the outputs passed unchanged into Solver.advance; pinned results; a solved window
 on the same handle left as it was; a refusal and an empty call on a live handle.  (tests/test_mv_raster_cpu.py holds the
@@ -46,6 +48,45 @@ def test_partly_filled_waves_and_the_scans_carry(solver):
     assert np.diff(got["rec_ptr"]).tolist() == list(M.COUNTS) and np.diff(got["q_ptr"]).tolist() == list(M.QUERY_COUNTS)
     big = got["rec_kept"][got["rec_ptr"][5]:]
     assert big[big >= 0].tolist() == list(range(got["kept_ptr"][6] - got["kept_ptr"][5]))
+
+
+def test_66_chunks_of_one_frame_and_two_tiles_per_thread(solver):
+    """one frame of 528 x 544 with 66 600 records and 2 000 queries: the carry of chunks 64 and 65 sums the counts of the chunks
+    before them over two wavefronts of k_mvr_keep's scan, and k_mvr_offsets gives every thread two of the 1 122 tiles and the
+    threads from 561 on none.  Every array against the numpy restatement; the first chunk's rows against the literal painting
+    and every 20th query against the sets."""
+    got = solver.mv_raster(M.chunks_case())
+    assert got["status"] == 0
+    ref = M.chunks_ref()
+    assert np.array_equal(got["kept_ptr"], ref["kept_ptr"]), (got["kept_ptr"].tolist(), ref["kept_ptr"].tolist())
+    M.compare(got, ref, "chunks")
+    M.compare_head(got)
+    kept = got["rec_kept"][got["rec_kept"] >= 0]
+    assert kept.tolist() == list(range(got["kept_ptr"][1])) and got["rec_kept"][-2:].tolist() == [-1, got["kept_ptr"][1] - 1]
+
+
+def test_record_counts_that_are_multiples_of_the_chunk(solver):
+    """1 024, 2 048 and 1 025 records: a last chunk that is full (the one that writes the frame's kept count), a workgroup that
+    finds the frame ended exactly where it would start, and a chunk of one skipped record"""
+    frames = M.multiples_case()
+    got = solver.mv_raster(frames)
+    M.compare(got, M.multiples_ref(), "multiples")
+    assert np.diff(got["rec_ptr"]).tolist() == list(M.MULTIPLES)
+    for f in range(3):
+        assert M.frame_rows(solver.mv_raster([frames[f]]), 0) == M.frame_rows(got, f), f
+
+
+def test_1024_frames_with_runs_of_empty_ones(solver):
+    """MOVBA_MAX_EXPRESS_IMAGES frames of 16 x 16 to 40 x 40 with 0 to 5 records and 0 to 3 queries: the scan over the frames in all
+    16 wavefronts, the tile scan across frames with four tiles per thread, the searches over rec_ptr, q_ptr and g_ptr through runs
+    of frames without records, queries or lattice.  kept_ptr in full, every array, and six frames alone against their rows."""
+    frames, ref = M.frames_case(), M.frames_ref()
+    got = solver.mv_raster(frames)
+    assert got["status"] == 0 and len(got["kept_ptr"]) == M.N_FRAMES + 1
+    assert np.array_equal(got["kept_ptr"], ref["kept_ptr"]), np.flatnonzero(got["kept_ptr"] != ref["kept_ptr"])[:8].tolist()
+    M.compare(got, ref, "frames")
+    for f in M.FRAMES_ALONE:
+        assert M.frame_rows(solver.mv_raster([frames[f]]), 0) == M.frame_rows(got, f) == M.frame_rows(ref, f), f
 
 
 def test_the_mixed_call_and_frame_by_frame_independence(solver):

@@ -1,5 +1,6 @@
 """movba_track_match on the device against the restatement of tests/track_match_ref.py, every comparison exact integer equality or
 equality of the payload's 64-bit words: the mixed call entry by entry with its -1 / NaN tails, the call at MOVBA_MAX_TRACK_SLOTS,
+the call at MOVBA_MAX_TRACK_QUERIES (the pack's sums over the query counts, which only the device runs, over every pass),
 the gather with and without its sources, the chain into movba_triangulate, independence of a query from everything but its own
 views and items (reordered, split over calls), pinned results, a solved window on the same handle left as it was, a refusal on
 a live handle and a call without queries."""
@@ -32,6 +33,25 @@ def test_one_view_at_the_slot_bound(solver):
     got = solver.track_match(*R.full_case())
     R.compare(got, R.full_ref(), "full")
     assert got["n_found"].tolist()[3:] == [len(R.full_case()[1][3][2]) - 2, 1, R.MAX_SLOTS]
+
+
+def test_4096_queries_take_the_sums_of_the_pack_over_every_pass(solver):
+    """MOVBA_MAX_TRACK_QUERIES queries of both modes over 64 views of 0 to 300 slots: k_tm_pack's sums over the counts of all
+    queries take 16 passes of their stride and all four wavefronts, which only the device runs (the host build keeps a running
+    count).  pair_ptr in full, every array with its tails, and queries 0, 255, 256, 257 and 4 095 alone against their rows."""
+    views, queries = R.many_case()
+    ref = R.many_ref()
+    got = solver.track_match(views, queries)
+    assert got["status"] == 0 and len(got["pair_ptr"]) == R.MANY_QUERIES + 1
+    assert np.array_equal(got["pair_ptr"], ref["pair_ptr"]), np.flatnonzero(got["pair_ptr"] != ref["pair_ptr"])[:8].tolist()
+    R.compare(got, ref, "many")
+    n = got["n_matches"]
+    assert 0 < n < len(got["match_slot1"]) and (got["match_slot1"][n:] == -1).all() and np.isnan(got["matches"]["ur2"][n:]).all()
+    want = R.rows(got, R.MANY_ALONE)
+    for q, row in zip(R.MANY_ALONE, want):
+        assert len(row[0]) >= 200, q
+        assert R.rows(solver.track_match(views, [queries[q]]), [0]) == [row], q
+        assert R.rows(R.ref_track_match(views, [queries[q]]), [0]) == [row], q          # (the literal double loop)
 
 
 def test_gather_copies_bits_and_pads_the_tails(solver):

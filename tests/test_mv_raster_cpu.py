@@ -18,17 +18,28 @@ from conftest import ROOT
 MVR_DIR = os.path.join(ROOT, "tests", "mv_raster")
 SAN_ENV = dict(ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1",
                TSAN_OPTIONS="halt_on_error=1")
-CASES = dict(full=(M.full_case, M.full_ref), pile=(M.pile_case, M.pile_ref), counts=(M.counts_case, M.counts_ref), mixed=(M.mixed_case, M.mixed_ref))
+CASES = dict(full=(M.full_case, M.full_ref), pile=(M.pile_case, M.pile_ref), counts=(M.counts_case, M.counts_ref), mixed=(M.mixed_case, M.mixed_ref),
+             multiples=(M.multiples_case, M.multiples_ref), frames=(M.frames_case, M.frames_ref), chunks=(M.chunks_case, M.chunks_ref))
+SMALL = [name for name in CASES if name != "chunks"]       # (what the literal and the set restatement walk in seconds)
+ALONE = dict(frames=M.FRAMES_ALONE, chunks=())              # the frames run alone too; every frame where nothing is said
 
 
 # ---- the restatements and their cases ------------------------------------------------------------------------------------------
 
 def test_the_two_restatements_agree_on_every_case():
-    for name, (case, ref) in CASES.items():
+    """... and the third, with numpy, equals both"""
+    for name in SMALL:
+        case, ref = CASES[name]
         M.compare(M.ref_mv_raster(case(), literal=False), ref(), name)
+        M.compare(M.ref_mv_raster(case(), vector=True), ref(), name + ", numpy")
+        M.compare(M.ref_mv_raster(case(), vector=True), M.ref_mv_raster(case(), literal=False), name + ", numpy against the sets")
     for threshold in (0.5, float(np.nextafter(0.5, 1))):
         M.compare(M.ref_mv_raster(M.gate_case(threshold), literal=False), M.ref_mv_raster(M.gate_case(threshold)), "gate")
+        M.compare(M.ref_mv_raster(M.gate_case(threshold), vector=True), M.ref_mv_raster(M.gate_case(threshold)), "gate, numpy")
     M.compare(M.ref_mv_raster(M.edge_case(), literal=False), M.ref_mv_raster(M.edge_case()), "edge")
+    M.compare(M.ref_mv_raster(M.edge_case(), vector=True), M.ref_mv_raster(M.edge_case()), "edge, numpy")
+    # the frame of 66 600 records: the literal painting of its first chunk and the sets at every 20th query
+    M.compare_head(M.chunks_ref())
 
 
 def test_full_case_meets_the_input_conditions():
@@ -107,6 +118,66 @@ def test_pile_counts_and_mixed_cases_are_what_the_gpu_tests_ask_for():
     ref = M.ref_mv_raster(M.gate_case(0.5))
     assert ref["cover_px"].tolist() == [2048] and ref["coverage_area"].tolist() == [0.5] and ref["force_grid"].tolist() == [0]
     assert M.ref_mv_raster(M.gate_case(float(np.nextafter(0.5, 1))))["force_grid"].tolist() == [1]
+
+
+def _tiles(fr):
+    return ((fr["rows"] + 15) // 16) * ((fr["cols"] + 15) // 16)
+
+
+def test_chunks_multiples_and_frames_cases_are_what_the_gpu_tests_ask_for():
+    """the inputs that take the scans only the device runs - the carry over a frame's chunks, the sums over frames and over tiles -
+    past their first wavefront, onto their edges and over runs of empty frames"""
+    # many chunks
+    (fr,), ref = M.chunks_case(), M.chunks_ref()
+    n = len(fr["records"]["w"])
+    assert (fr["rows"], fr["cols"]) == (528, 544) and _tiles(fr) == 33 * 34 == 1122
+    per = (1122 + 1023) // 1024
+    assert per == 2 and 561 * per >= 1122 > 560 * per                    # two tiles per thread, none from thread 561 on
+    assert n == 66600 and (n + 1023) // 1024 == 66 and n - 65 * 1024 == 40 and fr["want_grid"] == 1
+    rec_kept = ref["rec_kept"]
+    for a, b in ((0, 64 * 1024), (64 * 1024, 65 * 1024), (65 * 1024, n)):           # chunks 0 - 63, chunk 64, chunk 65
+        assert (rec_kept[a:b] >= 0).any() and (rec_kept[a:b] == -1).any(), (a, b)
+    per_chunk = [int((rec_kept[c * 1024:(c + 1) * 1024] >= 0).sum()) for c in range(66)]
+    assert all(0 < k < 1024 for k in per_chunk[:65]) and 0 < per_chunk[65] < 40
+    # (the carry of chunk 65 is a sum over lanes of wave 0 and one lane of wave 1; dropping wave 0's part moves every index)
+    assert rec_kept[65 * 1024:][rec_kept[65 * 1024:] >= 0][0] == sum(per_chunk[:65]) > 64 * 900
+    assert 1900 <= len(fr["q_pt"]) <= 2100
+    cand = ref["cand"]
+    assert (cand[:, 3] >= 0).sum() > 100 and (cand[:, 3] >= sum(per_chunk[:64])).any()    # the "largest" slot, from records of chunks 64 and 65 too
+    px = np.array(M.query_pixels(fr))
+    inside = (px[:, 0] >= 0) & (px[:, 1] >= 0) & (px[:, 0] < 544) & (px[:, 1] < 528)
+    assert ((cand == -1).all(axis=1) & inside).sum() > 20 and (~inside).any() and (cand[~inside] == -1).all()
+    assert (px[(cand == -1).all(axis=1) & inside][:, 1] >= M.CHUNKS_BAND).any()
+    assert set(ref["grid_covered"].tolist()) == {0, 1} and len(ref["grid_covered"]) == 32 * 33
+    assert ref["cover_px"][0] < 1 << 28
+    # exact multiples
+    frames, ref = M.multiples_case(), M.multiples_ref()
+    assert tuple(len(f["records"]["w"]) for f in frames) == M.MULTIPLES == (1024, 2048, 1025)
+    assert all((f["rows"], f["cols"]) == (64, 96) for f in frames)
+    for f in range(3):
+        a, b = int(ref["rec_ptr"][f]), int(ref["rec_ptr"][f + 1])
+        for c in range(a, b, 1024):
+            assert (ref["rec_kept"][c:min(c + 1024, b)] == -1).any(), (f, c)          # a skipped record in every chunk
+    assert ref["rec_kept"][1023] == ref["kept_ptr"][1] - 1 >= 0                       # the last record of a full last chunk is kept
+    assert ref["rec_kept"][1024 + 2047] == ref["kept_ptr"][2] - ref["kept_ptr"][1] - 1 >= 0
+    assert ref["rec_kept"][-1] == -1
+    # many frames
+    frames, ref = M.frames_case(), M.frames_ref()
+    assert len(frames) == M.N_FRAMES == 1024
+    assert all(16 <= f["rows"] <= 40 and 16 <= f["cols"] <= 40 for f in frames) and {f["rows"] for f in frames} == set(range(16, 41))
+    n_rec, n_q = np.diff(ref["rec_ptr"]), np.diff(ref["q_ptr"])
+    assert n_rec.min() == 0 and n_rec.max() == 5 and n_q.min() == 0 and n_q.max() == 3
+    for counts, none in ((n_rec, M.FRAMES_NO_RECORDS), (n_q, M.FRAMES_NO_QUERIES)):
+        assert (counts[list(none)] == 0).all() and none[0] == 0 and none[-1] == 1023
+        zero = "".join("0" if c == 0 else "x" for c in counts[1:-1])
+        assert "x000" in zero and "000x" in zero                                     # a run of at least 3 in the middle
+    assert sum(_tiles(f) for f in frames) > 1024
+    kept = np.diff(ref["kept_ptr"])
+    assert all((kept[64 * w:64 * (w + 1)] > 0).any() for w in range(16))             # every wavefront of the frame scan holds a count
+    assert (kept < n_rec).any() and ((kept == 0) & (n_rec > 0)).any()
+    assert M.FRAMES_ALONE == (0, 63, 64, 65, 511, 1023) and all(n_rec[f] > 0 and n_q[f] > 0 for f in (63, 64, 65, 511))
+    assert (np.diff(ref["grid_ptr"]) == 0).any() and (np.diff(ref["grid_ptr"]) > 0).any() and ref["grid_covered"].any()
+    assert (ref["cand"] >= 0).any() and set(ref["force_grid"].tolist()) == {0, 1}
 
 
 # ---- C-ABI without a device ------------------------------------------------------------------------------------------------
@@ -243,8 +314,8 @@ def test_the_librarys_steps_on_every_case(mvr_main, tmp_path, case):
     frames, ref = CASES[case][0](), CASES[case][1]()
     M.compare(run_mvr_main(mvr_main, frames, tmp_path), ref, case)
     # every frame alone: its arrays are the whole buffers, so a read behind them is seen
-    for f, fr in enumerate(frames):
-        M.compare(run_mvr_main(mvr_main, [fr], tmp_path), M.ref_mv_raster([fr]), f"{case}, frame {f} alone")
+    for f in ALONE.get(case, range(len(frames))):
+        M.compare(run_mvr_main(mvr_main, [frames[f]], tmp_path), M.ref_mv_raster([frames[f]]), f"{case}, frame {f} alone")
 
 
 def test_the_librarys_steps_on_the_gate_and_the_edge(mvr_main, tmp_path):

@@ -118,6 +118,40 @@ def test_full_case_is_what_the_gpu_test_asks_for():
     assert np.array_equal(ref["item_slot"][a:], np.arange(R.MAX_SLOTS))                  # LOOKUP does not look at taken
 
 
+def test_many_case_is_what_the_gpu_test_asks_for():
+    """what takes k_tm_pack's sums over the query counts (stride 256) through all their passes and over every wavefront"""
+    views, queries = R.many_case()
+    ref = R.many_ref()
+    assert len(queries) == R.MANY_QUERIES == 4096 and len(views) == 64
+    sizes = [len(v["track"]) for v in views]
+    assert min(sizes) == 0 and max(sizes) == 300 and len(set(sizes)) > 40
+    counts = np.diff(ref["pair_ptr"])
+    modes = np.array([q[0] for q in queries])
+    # non-zero counts in the first pass of the stride, in the second and in the last
+    assert (counts[:256] > 0).any() and (counts[256:512] > 0).any() and (counts[3841:] > 0).any()
+    # ... and in every wavefront of every pass but few (a wrong wave term moves pair_ptr)
+    assert ((counts.reshape(16, 4, 64) > 0).sum(axis=2) > 0).all()
+    # both modes interleaved: neither runs for more than a few queries; LOOKUP queries count 0 between queries that match
+    assert (modes == T).sum() > 1500 and (modes == L).sum() > 1500
+    runs = np.diff(np.flatnonzero(np.diff(modes) != 0))
+    assert runs.max() <= 12
+    assert (counts[modes == L] == 0).all()
+    between = [q for q in range(1, 4095) if modes[q] == L and counts[q - 1] > 0 and counts[q + 1] > 0]
+    assert len(between) > 100
+    # TRIANGULATION queries without a match and with several hundred
+    assert (counts[modes == T] == 0).sum() > 10 and counts.max() >= 200
+    for q in R.MANY_ALONE:
+        assert modes[q] == T and counts[q] >= 200, q
+    assert R.MANY_ALONE == (0, 255, 256, 257, 4095)
+    # LOOKUP queries with and without items, items found and absent
+    n_items = np.diff(ref["query_ptr"])
+    assert (n_items[modes == L] == 0).any() and (n_items > 0).any() and 0 < ref["n_found"].sum() < n_items.sum()
+    # the padding tail is not empty
+    cap = len(ref["match_slot1"])
+    assert cap == sum(sizes[q[1]] for q in queries if q[0] == T) and 0 < ref["n_matches"] < cap
+    assert (ref["match_slot1"][ref["n_matches"]:] == -1).all()
+
+
 # ---- C-ABI without a device ------------------------------------------------------------------------------------------------
 
 def test_symbol_and_struct_layouts(built_lib, tmp_path):
@@ -274,6 +308,10 @@ def test_the_librarys_steps_on_the_mixed_case(tm_main, tmp_path):
 
 def test_the_librarys_steps_on_the_full_case(tm_main, tmp_path):
     R.compare(run_tm_main(tm_main, *R.full_case(), tmp_path), R.full_ref(), "full")
+
+
+def test_the_librarys_steps_on_the_many_case(tm_main, tmp_path):
+    R.compare(run_tm_main(tm_main, *R.many_case(), tmp_path), R.many_ref(), "many")
 
 
 def test_the_librarys_steps_on_the_chain_case(tm_main, tmp_path):

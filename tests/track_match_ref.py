@@ -1,7 +1,7 @@
 """movba_track_match restated from the rules of include/movba.h (what the CPU and GPU tests compare against), twice: literally - a
 double loop with `break` for TRIANGULATION, a first-insert dict for LOOKUP - and with a dict per searched view for the large
 case (tests/test_track_match_cpu.py shows the two equal on every small case); and the committed cases: the mixed call, the call
-at MOVBA_MAX_TRACK_SLOTS, the gather call and the chain into movba_triangulate.  Everything is integer or a copy of bits: every
+at MOVBA_MAX_TRACK_SLOTS, the call at MOVBA_MAX_TRACK_QUERIES, the gather call and the chain into movba_triangulate.  Everything is integer or a copy of bits: every
 comparison is exact equality.  Helper module: no tests here (tests/test_track_match_cpu.py, tests/test_gpu_track_match.py).
 
 A call is (views, queries) as movba.capi.track_desc takes them: views is a list of dicts with `track` and optionally `taken`,
@@ -272,3 +272,42 @@ def chain_case():
         views.append(slots(m["obs2"][a:b], m["ur2"][a:b], m["depth2"][a:b], ids[a:b], 20))
     queries = [(TM_TRIANGULATION, int(v1), int(v2)) for v1, v2 in sc["pairs"]["pair_view"]]
     return sc, views, queries
+
+
+MANY_QUERIES = 4096
+MANY_ALONE = (0, 255, 256, 257, 4095)
+
+
+@functools.lru_cache(maxsize=None)
+def many_case():
+    """MOVBA_MAX_TRACK_QUERIES queries over 64 views of 0 to 300 slots, both modes interleaved: k_tm_pack's sum over the query counts
+    takes 16 passes of its stride of 256 and every wavefront of it holds counts.  Ids come from one pool of 600 for all views, so
+    two views share a good part of theirs; views 1 and 2 are of 300 slots over a pool of 150 with nothing taken (several hundred
+    matches), views 0 and 3 are empty.  The first and the last query match, and so do queries 255 to 257."""
+    rng = np.random.default_rng(9400)
+    sizes = rng.integers(0, 301, 64)
+    sizes[[0, 3]] = 0
+    sizes[[1, 2]] = 300
+    views = []
+    for k, n in enumerate(sizes.tolist()):
+        pool = 150 if k in (1, 2) else 600
+        taken = np.zeros(n, np.uint8) if k in (1, 2) else (rng.random(n) < 0.3).astype(np.uint8)
+        v = dict(track=rng.integers(0, pool, n).astype(np.int32), taken=taken)
+        v.update(_payload(rng, n, k))
+        views.append(v)
+    T, L = TM_TRIANGULATION, TM_LOOKUP
+    queries = []
+    for q in range(MANY_QUERIES):
+        if q in (0, 255, 256, 257, MANY_QUERIES - 1):
+            queries.append((T, 1 + q % 2, 2 - q % 2))
+        elif q % 3 == 1 or rng.random() < 0.2:
+            view = int(rng.integers(0, 64))
+            queries.append((L, view, rng.integers(0, 600, int(rng.integers(0, 6))).astype(np.int32)))
+        else:
+            queries.append((T, int(rng.integers(0, 64)), int(rng.integers(0, 64))))
+    return views, queries
+
+
+@functools.lru_cache(maxsize=None)
+def many_ref():
+    return ref_track_match(*many_case(), literal=False)
