@@ -1281,6 +1281,116 @@ typedef struct {
  * its results, its marginals and later runs stay as they were. */
 int  movba_mv_raster(movba_handle *h, const movba_mv_raster_desc *desc, movba_mv_raster_result *res);
 
+/* Sparse pyramidal Lucas-Kanade for the points of many independent frames (streams) per call: cv::calcOpticalFlowPyrLK as the
+ * reference calls it in four places - every previous feature of an I-frame (MOVExtractor.cc:91, window 31), the relocalisation
+ * block (:196, window 31), the coverage features of every P-frame (:347, window 31: movba_advance's MOVBA_ADV_COVERAGE) and every
+ * keypoint of a stereo frame, left to right (Frame.cc:304, window 21) - all with 3 pyramid levels above the image,
+ * TermCriteria(COUNT + EPS, 20, 0.01), OPTFLOW_LK_GET_MIN_EIGENVALS and a minimum-eigenvalue threshold of 1e-4.  The pyramids
+ * of both images are built on the device, a wavefront walks each point from the top level down, and the gate that the extractor
+ * applies behind the call (:98, :354) comes back as `keep` with the dense list of the kept points.
+ * [opencv-upstream] OpenCV's source is not part of the reference tree: the rules below restate the non-SIMD path of OpenCV 4.6
+ * (lkpyramid.cpp, pyramids.cpp) as SURVEY.md marks such text, and they - not a library build - are the contract of this call. */
+#define MOVBA_LK_MAX_WIN      31
+#define MOVBA_LK_MAX_LEVEL     3
+#define MOVBA_LK_MAX_ITER     30
+#define MOVBA_LK_MAX_PIXELS   67108864  /* 2^26: the sum of rows * cols over the frames of a call; both pyramids of all of them
+                                           then take less than 2^28 bytes of the handle's device scratch and the two level-0
+                                           images 2^27 bytes of its staging buffer                                           */
+/* movba_lk_result::exit_code: why the loop at level 0 ended, or why it never ran */
+#define MOVBA_LK_EPS           1  /* |delta|^2 <= eps^2                                                                      */
+#define MOVBA_LK_OSCILLATION   2  /* delta + prevDelta below 0.01 on both axes: the stored point steps back by delta / 2     */
+#define MOVBA_LK_MAX_ITER_RAN  3  /* all max_iter iterations ran                                                             */
+#define MOVBA_LK_REJ_START    16  /* the window's corner is out of bounds at level 0 before anything is read: status 0, err 0 */
+#define MOVBA_LK_REJ_MIN_EIG  17  /* level 0: minEig < min_eig_threshold or D < FLT_EPSILON: status 0                         */
+#define MOVBA_LK_REJ_LOOP     18  /* the window's corner left the bounds inside the loop at level 0: status 0                 */
+
+typedef struct {
+    int32_t n_frames, pad;          /* 0 .. MOVBA_MAX_EXPRESS_IMAGES; frames are independent                                */
+    const uint8_t *const *prev_image, *const *next_image;  /* n_frames pointers each to 8-bit grey pixels, as
+                                       movba_express_desc::image; either may be NULL for a frame without points             */
+    const int32_t *rows, *cols;     /* n_frames each, both > win; the sum of rows * cols is at most MOVBA_LK_MAX_PIXELS      */
+    const int32_t *stride;          /* n_frames: bytes from one row to the next of BOTH images, >= cols                      */
+    const int32_t *win;             /* n_frames: winSize (square), odd, 3 .. MOVBA_LK_MAX_WIN; the reference: 31 and 21      */
+    const int32_t *pt_ptr;          /* n_frames + 1, ascending, [0] = 0: the points of frame f; n_pt = pt_ptr[n_frames] <=
+                                       MOVBA_MAX_EXPRESS_ITEMS                                                              */
+    const float   *pt;              /* n_pt x 2: prevPts, x y; finite, |.| <= 2^20                                          */
+    int32_t max_level, max_iter;    /* maxLevel 0 .. MOVBA_LK_MAX_LEVEL (3); TermCriteria::maxCount 1 .. MOVBA_LK_MAX_ITER (20) */
+    double  eps;                    /* TermCriteria::epsilon, finite, 0 < eps <= 10 (0.01)                                   */
+    double  min_eig_threshold;      /* minEigThreshold, finite, > 0 (1e-4)                                                   */
+} movba_lk_desc;   /* 96 bytes */
+
+typedef struct {
+    float   *next_pt;               /* n_pt x 2: nextPts                                                                    */
+    uint8_t *pt_status;             /* n_pt: the call's `status` vector, 1 or 0                                             */
+    float   *err;                   /* n_pt: the call's `err` vector: the minimum eigenvalue of the lowest level that formed
+                                       its matrix (0 without one), what OPTFLOW_LK_GET_MIN_EIGENVALS makes of it            */
+    uint8_t *exit_code;             /* n_pt: MOVBA_LK_*                                                                     */
+    uint8_t *keep;                  /* n_pt: pt_status && 0 <= next_pt.x < cols && 0 <= next_pt.y < rows                    */
+    int32_t *kept_ptr;              /* n_frames + 1: the kept points of frame f are entries [kept_ptr[f], kept_ptr[f + 1]) of
+                                       kept_src                                                                             */
+    int32_t *kept_src;              /* capacity n_pt, dense over the call: the index WITHIN THE FRAME of each kept point, in
+                                       input order - what the reference's push order makes dIndx; behind the total: -1      */
+    int32_t  status, pad;
+} movba_lk_result; /* 64 bytes */
+
+/* Restated as written [opencv-upstream], per frame.  W = cols, H = rows, win = the frame's window.
+ *   Pyramid  of each image: level 0 is the image; level l + 1 has size ((w + 1) / 2, (h + 1) / 2) and pixel (x, y) =
+ *            (sum over i, j in 0 .. 4 of k[i] k[j] src(r(2x + i - 2), r(2y + j - 2)) + 128) >> 8, k = [1 4 6 4 1], r the
+ *            BORDER_REFLECT_101 index (-1 -> 1, w -> w - 2) on the source level; all integer.  The levels used are 0 .. L, L
+ *            the largest value <= max_level such that every level 1 .. L has both sides > win (buildOpticalFlowPyramid stops
+ *            there).
+ *   Reads    a pixel outside a level is the REFLECT_101 pixel.  The derivative is Scharr, unscaled int16: Ix = 3 d(y - 1) +
+ *            10 d(y) + 3 d(y + 1) with d(y) = p(x + 1, y) - p(x - 1, y), Iy the transpose, with REFLECT_101 neighbours at a
+ *            position inside the level; at a position OUTSIDE the level the derivative is 0, the constant border of the
+ *            derivative buffer.  Both pyramids carry a border of win pixels, which the bounds test below never leaves.
+ *   Point    status = 1; for l = L .. 0 on level l (w_l x h_l):
+ *     Start    prevPt = pt * 2^-l, exact.  nextPt = prevPt at level L, else 2 * nextPt; it is stored.  half = (win - 1) * 0.5f;
+ *              p = prevPt - half; ip = floor(p).  If ip.x < -win || ip.x >= w_l || ip.y < -win || ip.y >= h_l: at level 0 status
+ *              = 0, err = 0, MOVBA_LK_REJ_START; on to the next level - an upper level that fails leaves the stored point as it
+ *              is and the walk continues.
+ *     Weights  a = p.x - ip.x, b = p.y - ip.y in fp32; iw00 = rint((1 - a)(1 - b) * 16384), iw01 = rint(a (1 - b) * 16384), iw10
+ *              = rint((1 - a) b * 16384), to nearest with ties to even; iw11 = 16384 - iw00 - iw01 - iw10.
+ *     Patch    for (x, y) in win x win: I = descale(p(ip + (x, y)) iw00 + p(+ (1, 0)) iw01 + p(+ (0, 1)) iw10 + p(+ (1, 1))
+ *              iw11, 9) on the previous image, Ix and Iy = descale(the same sum over the derivative, 14); descale(v, n) = (v +
+ *              (1 << (n - 1))) >> n, an arithmetic shift.  |Ix|, |Iy| <= 4080, I <= 8160.
+ *     Sums     A11 = sum Ix^2, A12 = sum Ix Iy, A22 = sum Iy^2 and, in the loop, b1 = sum diff Ix, b2 = sum diff Iy are EXACT
+ *              integers (961 terms stay below 2^36), converted once to fp32 and multiplied by 2^-20.  OpenCV keeps fp32 running
+ *              sums whose value depends on its SIMD width: the exact sum is the one place where the call is more definite than
+ *              the reference.
+ *     Matrix   in fp32, one rounding per operation: D = A11 A22 - A12^2; minEig = (A22 + A11 - sqrt((A11 - A22)^2 + 4 A12^2)) /
+ *              (2 win win); err = minEig.  If minEig < min_eig_threshold (compared in fp64) or D < FLT_EPSILON: at level 0
+ *              status = 0, MOVBA_LK_REJ_MIN_EIG; on to the next level.  D = 1 / D.
+ *     Loop     nextPt -= half; for j = 0 .. max_iter - 1: ip = floor(nextPt); the bounds test of Start - at level 0 status = 0
+ *              (MOVBA_LK_REJ_LOOP) - break.  Weights from nextPt.  diff = descale(the weighted sum over the NEXT image, 9) - I.
+ *              delta = ((A12 b2 - A22 b1) D, (A12 b1 - A11 b2) D); nextPt += delta; nextPt + half is stored.  Break if
+ *              (double)dx^2 + (double)dy^2 <= eps^2 (MOVBA_LK_EPS).  If j > 0 && |dx + prevdx| < 0.01 && |dy + prevdy| < 0.01
+ *              (the fp32 sums against the fp64 constant): the stored point -= delta * 0.5f; break (MOVBA_LK_OSCILLATION).
+ *              prevDelta = delta.  Otherwise MOVBA_LK_MAX_ITER_RAN.  The bounds tests compare floor()'s float, so a point that
+ *              has run beyond the integers fails them like any other.
+ *     With OPTFLOW_LK_GET_MIN_EIGENVALS nothing runs behind the loop: no final bounds test and no patch error.
+ *   keep     pt_status && 0 <= next_pt.x < W && 0 <= next_pt.y < H on the fp32 values (:98, :354); kept_ptr and kept_src
+ *            list the kept points in input order.
+ * What stays with the caller: the choice of the points and of the image pair; the feature construction behind :98 and :354
+ * (track ids, ages, descriptors: movba_express's DESCRIBE on the new rect); relocalisation's choice of the best point (:196 on);
+ * the stereo gates of Frame.cc:306-353 (row difference, disparity range, depth) on next_pt, pt_status and err.
+ * A frame's result depends on that frame's data alone, a point's on its frame's images, window and its own coordinates, and two
+ * calls give the same bits.
+ * Returns MOVBA_ERR_ARG for a NULL handle, descriptor or result; n_frames negative or above MOVBA_MAX_EXPRESS_IMAGES; pt_ptr NULL
+ * or not ascending from 0; n_pt above MOVBA_MAX_EXPRESS_ITEMS; a NULL array that the counts make necessary (prev_image,
+ * next_image, rows, cols, stride, win always, pt when n_pt > 0), or a NULL result array; a NULL image pointer for a frame that has
+ * points; win even or outside 3 .. MOVBA_LK_MAX_WIN; rows or cols <= win (so that one reflection always suffices at level 0);
+ * stride < cols; a sum of rows * cols above MOVBA_LK_MAX_PIXELS; max_level outside 0 .. 3, max_iter outside 1 .. 30; eps not
+ * finite, <= 0 or > 10 (beyond which OpenCV clamps it); min_eig_threshold not finite or <= 0; a pt that is not finite or above
+ * 2^20 in magnitude.  MOVBA_ERR_HIP as elsewhere.  Every argument is checked before anything is queued, and on a non-zero status
+ * nothing is written except `status`.  n_frames == 0: MOVBA_OK and nothing else written.
+ * One packed copy to the device - level 0 of both images of the frames that have points, row by row without the stride's
+ * padding - at most five launches - k_lk_pyr per level 1 .. 3 (a thread per pixel), k_lk_track (a wavefront per point: lane t
+ * owns window entries t, t + 64, ..., integer wave sums, the same fp32 tail in every lane) and k_lk_keep (a workgroup per frame:
+ * kept_ptr, kept_src) - and one synchronisation; result arrays that lie in movba_host_alloc memory are written by the kernels
+ * themselves.  May share a handle with an uploaded or solved window, waiting for the window's arrays before it reuses the
+ * staging buffer: the window, its results, its marginals and later runs stay as they were. */
+int  movba_lk_track(movba_handle *h, const movba_lk_desc *desc, movba_lk_result *res);
+
 #ifdef __cplusplus
 }
 #endif

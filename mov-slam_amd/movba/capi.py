@@ -218,6 +218,24 @@ class MvRasterResult(C.Structure):
                 ("pad", C.c_int32)]
 
 
+class LkDesc(C.Structure):
+    _fields_ = [("n_frames", C.c_int32), ("pad", C.c_int32), ("prev_image", C.POINTER(C.c_void_p)), ("next_image", C.POINTER(C.c_void_p)),
+                ("rows", _i), ("cols", _i), ("stride", _i), ("win", _i), ("pt_ptr", _i), ("pt", _f), ("max_level", C.c_int32),
+                ("max_iter", C.c_int32), ("eps", C.c_double), ("min_eig_threshold", C.c_double)]
+
+
+class LkResult(C.Structure):
+    _fields_ = [("next_pt", _f), ("pt_status", _u), ("err", _f), ("exit_code", _u), ("keep", _u), ("kept_ptr", _i), ("kept_src", _i),
+                ("status", C.c_int32), ("pad", C.c_int32)]
+
+
+# (key, dtype, width, which count it is sized by) of movba_lk_result
+LK_ARRAYS = (("next_pt", np.float32, 2, "pt"), ("pt_status", np.uint8, 1, "pt"), ("err", np.float32, 1, "pt"),
+             ("exit_code", np.uint8, 1, "pt"), ("keep", np.uint8, 1, "pt"), ("kept_ptr", np.int32, 1, "ptr"), ("kept_src", np.int32, 1, "pt"))
+# movba_lk_result::exit_code (MOVBA_LK_*) and the bounds of movba_lk_desc
+LK_EPS, LK_OSCILLATION, LK_MAX_ITER_RAN = 1, 2, 3
+LK_REJ_START, LK_REJ_MIN_EIG, LK_REJ_LOOP = 16, 17, 18
+LK_MAX_WIN, LK_MAX_LEVEL, LK_MAX_ITER, LK_MAX_PIXELS = 31, 3, 30, 1 << 26
 # (key, dtype, width, which count it is sized by) of movba_mv_raster_result
 MV_RASTER_ARRAYS = (("kept_ptr", np.int32, 1, "ptr"), ("kp_rect", np.int32, 4, "rec"), ("mv_pt", np.float32, 2, "rec"),
                     ("mv_dindx", np.int32, 1, "rec"), ("rec_kept", np.int32, 1, "rec"), ("cand", np.int32, 4, "q"),
@@ -292,7 +310,7 @@ EXPORTS = ["movba_version", "movba_status_string", "movba_create", "movba_destro
            "movba_host_alloc", "movba_host_free", "movba_dense_plan_probe", "movba_pose_opt_batch", "movba_lba_marginals", "movba_triangulate",
            "movba_two_view", "movba_two_view_samples", "movba_two_view_lo", "movba_init_map", "movba_view_points",
            "movba_point_normals", "movba_lba_point_normals", "movba_covisibility", "movba_track_match", "movba_express",
-           "movba_express_grid", "movba_advance", "movba_mv_raster"]
+           "movba_express_grid", "movba_advance", "movba_mv_raster", "movba_lk_track"]
 
 _libs = {False: None, True: None}
 
@@ -362,6 +380,7 @@ def lib(hooks: bool = False):
         L.movba_express_grid.argtypes = [C.c_int32, C.c_int32, _i, C.c_int32]
         L.movba_advance.argtypes = [C.c_void_p, C.POINTER(AdvanceDesc), C.POINTER(AdvanceResult)]
         L.movba_mv_raster.argtypes = [C.c_void_p, C.POINTER(MvRasterDesc), C.POINTER(MvRasterResult)]
+        L.movba_lk_track.argtypes = [C.c_void_p, C.POINTER(LkDesc), C.POINTER(LkResult)]
         L.movba_host_alloc.argtypes = [C.c_size_t]
         L.movba_host_alloc.restype = C.c_void_p
         L.movba_dense_plan_probe.argtypes = [C.c_int32, C.c_int32, C.c_int32, _i, _i, C.c_int32, _i, C.c_int32]
@@ -918,6 +937,53 @@ def mv_raster_result(n_frames, n_records, n_q, n_grid, alloc=np.zeros):
     return r, keep
 
 
+def lk_desc(frames, max_level=3, max_iter=20, eps=0.01, min_eig_threshold=1e-4):
+    """frames: one dict per frame with prev and next (2-D uint8 of one shape, any row stride but the same in both; None for a
+    frame without points, then with rows and cols), win and pt (n, 2) -> (movba_lk_desc, the arrays it points into)."""
+    nf = len(frames)
+    keep = dict(images=[], rows=np.ones(nf, np.int32), cols=np.ones(nf, np.int32), stride=np.ones(nf, np.int32),
+                win=np.array([fr["win"] for fr in frames], np.int32).reshape(nf), prev_image=(C.c_void_p * max(nf, 1))(),
+                next_image=(C.c_void_p * max(nf, 1))())
+    for i, fr in enumerate(frames):
+        a, b = fr.get("prev"), fr.get("next")
+        if a is None or b is None:
+            keep["rows"][i], keep["cols"][i] = fr["rows"], fr["cols"]
+            keep["stride"][i] = fr["cols"]
+            continue
+        for im in (a, b):
+            if im.dtype != np.uint8 or im.ndim != 2 or (im.shape[1] > 1 and im.strides[1] != 1):
+                raise ValueError("lk_desc: an image is a 2-D uint8 array whose rows are contiguous")
+        if a.shape != b.shape or a.strides[0] != b.strides[0]:
+            raise ValueError("lk_desc: the two images of a frame have one shape and one row stride")
+        keep["images"] += [a, b]
+        keep["prev_image"][i], keep["next_image"][i] = a.ctypes.data, b.ctypes.data
+        keep["rows"][i], keep["cols"][i] = a.shape
+        keep["stride"][i] = a.strides[0] if a.shape[0] > 1 else a.shape[1]
+    parts = [np.asarray(fr["pt"], np.float32).reshape(-1, 2) for fr in frames]
+    keep["pt_ptr"] = np.concatenate([[0], np.cumsum([len(a) for a in parts])]).astype(np.int32)
+    keep["pt"] = np.ascontiguousarray(np.concatenate(parts) if parts else np.zeros((0, 2)), np.float32)
+    d = LkDesc()
+    d.n_frames = nf
+    d.prev_image = C.cast(keep["prev_image"], C.POINTER(C.c_void_p))
+    d.next_image = C.cast(keep["next_image"], C.POINTER(C.c_void_p))
+    for key in ("rows", "cols", "stride", "win", "pt_ptr"):
+        setattr(d, key, _p(keep[key], _i))
+    d.pt = _p(keep["pt"], _f)
+    d.max_level, d.max_iter, d.eps, d.min_eig_threshold = max_level, max_iter, eps, min_eig_threshold
+    return d, keep
+
+
+def lk_result(n_frames, n_pt, alloc=np.zeros):
+    """-> (movba_lk_result with its output arrays, the arrays it points into)"""
+    size = dict(pt=n_pt, ptr=n_frames + 1)
+    types = {np.int32: _i, np.uint8: _u, np.float32: _f}
+    keep, r = {}, LkResult()
+    for key, dtype, width, which in LK_ARRAYS:
+        keep[key] = alloc((size[which], width) if width > 1 else (size[which],), dtype)
+        setattr(r, key, _p(keep[key], types[dtype]))
+    return r, keep
+
+
 def run_batch(solvers) -> int:
     """movba_lba_run_batch over the resident windows of `solvers` (created on one stream); download each as usual."""
     arr = (C.c_void_p * len(solvers))(*[s._h for s in solvers])
@@ -1370,6 +1436,19 @@ class Solver:
         if rc < 0:
             raise MovbaError(f"movba_mv_raster: {status_string(rc)}")
         out.update(status=rc, rec_ptr=keep["rec_ptr"], q_ptr=keep["q_ptr"])
+        return out
+
+    def lk_track(self, frames, max_level=3, max_iter=20, eps=0.01, min_eig_threshold=1e-4, pinned=False) -> dict:
+        """movba_lk_track (sparse pyramidal Lucas-Kanade, cv::calcOpticalFlowPyrLK as the reference calls it, for the points of
+        many frames): frames as lk_desc -> dict(status, next_pt (n_pt, 2), pt_status, err, exit_code, keep (n_pt,), kept_ptr
+        (n_frames + 1,), kept_src (n_pt, padded with -1 behind kept_ptr[-1]), pt_ptr).  The defaults are the reference's.
+        pinned: result arrays in movba_host_alloc memory, written by the kernels themselves."""
+        d, keep = lk_desc(frames, max_level, max_iter, eps, min_eig_threshold)
+        r, out = lk_result(d.n_frames, len(keep["pt"]), self._pinned if pinned else np.zeros)
+        rc = self._L.movba_lk_track(self._h, C.byref(d), C.byref(r))
+        if rc < 0:
+            raise MovbaError(f"movba_lk_track: {status_string(rc)}")
+        out.update(status=rc, pt_ptr=keep["pt_ptr"])
         return out
 
     def lba_point_normals(self, ref_pose, ref_level, scale_factors, outlier=None, pinned=False) -> dict:
