@@ -365,10 +365,12 @@ int movba_version(void) { return MOVBA_VERSION; }
 #ifdef MOVBA_TEST_HOOKS
 // Test build only (libmovba_hooks.so; declared by the tests themselves, not by include/movba.h): sets one hook of a handle.
 // "device_cus" plans the one-launch direct solver for a device with fewer compute units than this one has.
+// "batch_variant" sets nothing: it returns TestHooks::batch_variant, the record of the last batched run, as a code >= 0.
 int movba_test_hook(movba_handle *h, const char *name, long long value)
 {
     if (!h || !name) return MOVBA_ERR_ARG;
     const std::string n(name);
+    if (n == "batch_variant") return h->hooks.batch_variant;
     if (n == "host_structure") h->hooks.host_structure = (int)value;
     else if (n == "host_grouping") h->hooks.host_grouping = (int)value;
     else if (n == "entries_unpacked") h->hooks.entries_unpacked = (int)value;
@@ -814,9 +816,18 @@ int movba_lba_run_batch(movba_handle *const *hs, int32_t n)
     for (int i = 0; i < n; ++i) {
         movba_handle *h = hs[i];
         h->ran = false; h->run_status = MOVBA_OK; h->export_in_run = false; h->early_setup = false;      // (the batch queues every window's setup itself)
+#ifdef MOVBA_TEST_HOOKS
+        h->hooks.batch_variant = 0;
+#endif
         if (h->early_status != MOVBA_OK) { h->ran = true; continue; }
         if (caller_stop(h->stop)) { h->run_status = MOVBA_STOPPED; h->ran = true; continue; }
-        if (!h->rows_kernel || h->win.kcam) { solo.push_back(h); continue; }      // (direct-solver windows and windows with intrinsics by keyframe run on their own)
+        if (!h->rows_kernel || h->win.kcam) {       // (direct-solver windows and windows with intrinsics by keyframe run on their own)
+#ifdef MOVBA_TEST_HOOKS
+            h->hooks.batch_variant = 1 << 9;
+#endif
+            solo.push_back(h);
+            continue;
+        }
         act.push_back(h);
     }
     const int na = (int)act.size();
@@ -839,6 +850,13 @@ int movba_lba_run_batch(movba_handle *const *hs, int32_t n)
             for (hipEvent_t &e : h0->batch_ev) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
             for (auto &ring : h0->batch_phase_ev) for (hipEvent_t &e : ring) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
         }
+#ifdef MOVBA_TEST_HOOKS
+        {   // (test build: the template arguments of this call's launches, on every handle of the call that reached this point)
+            const int fold = (ldsp ? 1 : 0) | (overflow ? 2 : 0) | (padded && !overflow ? 4 : 0) | (stereo ? 8 : 0) | (ngroups << 4);
+            for (movba_handle *h : act) h->hooks.batch_variant = fold | (1 << 8);
+            for (movba_handle *h : solo) h->hooks.batch_variant |= fold;
+        }
+#endif
         // the second group runs on the device's shared copy stream (idle during a run): every stream the process creates
         // competes for the few hardware queues, and two groups that land on one queue run in turns (measured: 2.3 -> 3.7 ms)
         for (int g = 2; g < ngroups; ++g)

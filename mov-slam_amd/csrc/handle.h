@@ -91,6 +91,10 @@ struct TestHooks {
     int helper_delay_us = 0;        // the upload's helper thread starts that much later (its early-setup launches too)
     long long wait_ticks = -1;      // >= 0: bound of the in-launch waits of a run's FIRST attempt (10 ns ticks)
     int band_park_trial = -1;       // >= 0: k_band treats that trial's factorisation as one that met a non-positive pivot
+    // what the last movba_lba_run_batch over this handle launched with (written by the call, read as hook "batch_variant"):
+    // bit 0 ldsp, 1 overflow, 2 padded, 3 stereo (the fold over the batched windows; 0 where none was batched), bits 4-7 the
+    // number of stream groups, bit 8: the window was in the batched launches, bit 9: it ran on its own behind them
+    int batch_variant = 0;
 };
 #ifdef MOVBA_TEST_HOOKS
 #define HOOK(h, field) ((h)->hooks.field)

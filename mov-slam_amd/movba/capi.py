@@ -1012,12 +1012,21 @@ class Solver:
 
     def hook(self, name: str, value: int):
         """movba_test_hook (test build only: Solver(hooks=True)): host_structure, entries_unpacked, no_sorted_structure,
-        pcg_packed, helper_delay_us, wait_ticks, band_park_trial, device_cus"""
+        pcg_packed, helper_delay_us, wait_ticks, band_park_trial, device_cus set a switch and return 0; batch_variant sets
+        nothing and returns what the last movba_lba_run_batch over this handle launched with (decode with batch_variant())"""
         if not self._hooks:
             raise MovbaError("test hooks exist in libmovba_hooks.so only: Solver(hooks=True)")
         rc = self._L.movba_test_hook(self._h, name.encode(), int(value))
-        if rc != OK:
+        if rc < 0:
             raise MovbaError(f"movba_test_hook({name}): {status_string(rc)}")
+        return rc
+
+    def batch_variant(self) -> dict:
+        """The record of the last batched run (test build only): the kernel variant every batched launch took - ldsp, overflow,
+        padded, stereo: the fold over the batch's windows -, the number of stream groups, and where this window ran."""
+        v = self.hook("batch_variant", 0)
+        return dict(ldsp=v & 1, overflow=(v >> 1) & 1, padded=(v >> 2) & 1, stereo=(v >> 3) & 1, groups=(v >> 4) & 15,
+                    batched=(v >> 8) & 1, solo=(v >> 9) & 1)
 
     def stamp_records(self, cls: int):
         """movba_stamp_records (clock-stamp build only, -DMOVBA_CLOCK_STAMP; not in include/movba.h): the records the last run left,

@@ -35,7 +35,7 @@ def test_product_library_reads_only_its_documented_process_switches(built_lib):
     names = set(m.decode() for m in re.findall(rb"MOVBA_[A-Z_0-9]{3,}", blob))
     allowed = {"MOVBA_WATCHDOG_MS", "MOVBA_TIME_UPLOAD", "MOVBA_TIME_SOLVE", "MOVBA_DENSE_STAMPS", "MOVBA_DENSE_MULTILAUNCH", "MOVBA_BAND", "MOVBA_BATCH_GROUPS"}
     assert names <= allowed, names - allowed
-    for hook in (b"band_park_trial", b"helper_delay_us", b"host_structure", b"movba_test_hook"):
+    for hook in (b"band_park_trial", b"batch_variant", b"helper_delay_us", b"host_structure", b"movba_test_hook"):
         assert hook not in blob and hook in open(built_lib.HOOKS_LIB_PATH, "rb").read()
     src = open(os.path.join(ROOT, "mov-slam_amd", "csrc", "api.cpp")).read()
     assert src.count("std::getenv(") == len(allowed)          # all of them inside process_switches()
