@@ -1372,7 +1372,8 @@ typedef struct {
  *            list the kept points in input order.
  * What stays with the caller: the choice of the points and of the image pair; the feature construction behind :98 and :354
  * (track ids, ages, descriptors: movba_express's DESCRIBE on the new rect); relocalisation's choice of the best point (:196 on);
- * the stereo gates of Frame.cc:306-353 (row difference, disparity range, depth) on next_pt, pt_status and err.
+ * the stereo gates of Frame.cc:306-353 (row difference, disparity range, depth, the median rule) are movba_stereo_points, which
+ * takes pt, next_pt and pt_status as they are.
  * A frame's result depends on that frame's data alone, a point's on its frame's images, window and its own coordinates, and two
  * calls give the same bits.
  * Returns MOVBA_ERR_ARG for a NULL handle, descriptor or result; n_frames negative or above MOVBA_MAX_EXPRESS_IMAGES; pt_ptr NULL
@@ -1390,6 +1391,119 @@ typedef struct {
  * themselves.  May share a handle with an uploaded or solved window, waiting for the window's arrays before it reuses the
  * staging buffer: the window, its results, its marginals and later runs stay as they were. */
 int  movba_lk_track(movba_handle *h, const movba_lk_desc *desc, movba_lk_result *res);
+
+/* Stereo depths and new map points for the keypoints of many independent stereo frames per call: what the reference does
+ * between the left-to-right LK call and the use of mvuRight / mvDepth - the gates of Frame::ComputeStereoMatches behind the LK
+ * call (Frame.cc:306-338), its median-distance pruning (:340-353), Frame::UnprojectStereo (:836-851) and the choice of the
+ * points that Tracking::StereoInitialization (Tracking.cc:532-547), Tracking::CreateNewKeyFrame (:1022-1098) and
+ * Tracking::UpdateLastFrame (:828-887) turn into map points.  It takes movba_lk_track's arrays as they are and gives u_right
+ * and depth in the layout that movba_lba_solve (obs_right), movba_triangulate (ur1 / depth1) and movba_track_match read.
+ * Arithmetic marked [opencv-upstream] restates OpenCV 4.6 as SURVEY.md marks such text. */
+#define MOVBA_MAX_STEREO_POINTS 16384   /* keypoints of one frame: what one workgroup sorts in LDS (8-byte keys, 128 KiB) */
+/* movba_stereo_desc::select */
+#define MOVBA_STEREO_SELECT_NONE   0  /* depths only                                                                          */
+#define MOVBA_STEREO_SELECT_ALL    1  /* StereoInitialization: every point with depth > 0, in index order; all are new        */
+#define MOVBA_STEREO_SELECT_CLOSE  2  /* CreateNewKeyFrame / UpdateLastFrame: by depth, up to th_depth and max_point          */
+/* movba_stereo_result::code */
+#define MOVBA_STEREO_OK             1
+#define MOVBA_STEREO_REJ_STATUS    16  /* pt_status 0 or next_pt outside the right image                                       */
+#define MOVBA_STEREO_REJ_ROW       17  /* |next_pt.y - pt.y| > max_row_diff                                                    */
+#define MOVBA_STEREO_REJ_DISPARITY 18  /* pt.x - next_pt.x outside [min_disparity, max_disparity)                              */
+#define MOVBA_STEREO_REJ_FAR       19  /* accepted by the gates, pruned by the median rule                                     */
+
+typedef struct {
+    int32_t n_frames, pad;          /* 0 .. MOVBA_MAX_EXPRESS_IMAGES; frames are independent                                */
+    const int32_t *pt_ptr;          /* n_frames + 1, ascending, [0] = 0: the points of frame f, at most MOVBA_MAX_STEREO_POINTS
+                                       of them; n_pt = pt_ptr[n_frames] <= MOVBA_MAX_EXPRESS_ITEMS - as movba_lk_desc          */
+    const float   *pt;              /* n_pt x 2: mvKeys[i].pt, the very array given to movba_lk_track; finite, |.| <= 2^20     */
+    const float   *next_pt;         /* n_pt x 2: movba_lk_result::next_pt; finite, |.| <= 2^20 where pt_status != 0           */
+    const uint8_t *pt_status;       /* n_pt: movba_lk_result::pt_status                                                      */
+    const float   *pt_un;           /* n_pt x 2 or NULL: mvKeysUn[i].pt, what is un-projected; NULL: pt (zero distortion)     */
+    const int32_t *rows, *cols;     /* n_frames each, >= 1: the RIGHT image's                                                */
+    const float   *bf;              /* n_frames: mbf, finite, > 0                                                            */
+    const float   *max_disparity;   /* n_frames: maxD, finite.  An input: the reference reads mb before it is assigned (below);
+                                       the intended value is mbf / (mbf / fx), computed in fp32                              */
+    const float   *th_depth;        /* n_frames: mThDepth, finite (read for MOVBA_STEREO_SELECT_CLOSE)                        */
+    const float   *cam;             /* n_frames x 4: fx fy cx cy, finite, fx fy > 0                                          */
+    const int32_t *select;          /* n_frames: MOVBA_STEREO_SELECT_*                                                       */
+    const double  *poses;           /* n_frames x 7 or NULL: Tcw as movba_view_desc::poses (qx qy qz qw tx ty tz, the quaternion
+                                       normalised first); NULL: the identity for every frame (SetPose(SE3f()), Tracking.cc:524) */
+    const uint8_t *has_point;       /* n_pt or NULL: 1 where mvpMapPoints[i] is a map point with at least one observation;
+                                       NULL: all 0                                                                           */
+    float   max_row_diff;           /* finite (4)                                                                            */
+    float   min_disparity;          /* minD, finite (0)                                                                      */
+    int32_t max_point, pad2;        /* maxPoint >= 0 (100)                                                                   */
+} movba_stereo_desc;   /* 136 bytes */
+
+typedef struct {
+    float   *u_right, *depth;       /* n_pt each: mvuRight, mvDepth; -1 where there is no stereo observation, after pruning   */
+    uint8_t *code;                  /* n_pt: MOVBA_STEREO_*                                                                  */
+    int32_t *n_stereo;              /* n_frames: the frame's points left with depth > 0                                      */
+    int32_t *median_dist;           /* n_frames: the upper median of the int distances; -1 without a candidate               */
+    float   *th_dist;               /* n_frames: thDist; 0 without a candidate                                               */
+    int32_t *sel_ptr;               /* n_frames + 1: the selected points of frame f are entries [sel_ptr[f], sel_ptr[f + 1]) of
+                                       the four arrays below, dense over the call                                            */
+    int32_t *sel_src;               /* capacity n_pt: the index WITHIN THE FRAME, in walk order; behind the total: -1         */
+    uint8_t *sel_new;               /* capacity n_pt: 1 where the walk creates a map point; behind the total: 0               */
+    float   *sel_cam;               /* capacity n_pt x 3: x y z of Frame.cc:843-845; behind the total: NaN                    */
+    double  *sel_point;             /* capacity n_pt x 3: x3D, world; behind the total: NaN                                   */
+    int32_t  status, pad;
+} movba_stereo_result; /* 96 bytes */
+
+/* Restated as written, per frame.  W = cols, H = rows of the right image.
+ *   Gates    per keypoint i, fp32, one rounding per operation; L = pt[i], R = next_pt[i]:
+ *     1  pt_status[i] == 0 || R.x < 0 || R.y < 0 || R.x >= (float)W || R.y >= (float)H: MOVBA_STEREO_REJ_STATUS (-0.0 passes).
+ *     2  fabsf(R.y - L.y) > max_row_diff: MOVBA_STEREO_REJ_ROW (std::abs(float): Frame.h:36 has `using namespace std`).
+ *     3  disparity = L.x - R.x; unless disparity >= min_disparity && disparity < max_disparity: MOVBA_STEREO_REJ_DISPARITY.
+ *     4  if disparity <= 0: disparity = (float)0.01 and bestUr = (float)((double)L.x - 0.01) - the source subtracts a double
+ *        literal; otherwise bestUr = R.x.
+ *     5  depth = bf / disparity; u_right = bestUr.
+ *     6  d = L - R in fp32; dist = (float)sqrt((double)d.x d.x + (double)d.y d.y) (cv::norm(Point2f), [opencv-upstream]), stored
+ *        into pair<int, int>: TRUNCATED to an int.
+ *     max_disparity: the reference computes mbf / mb (Frame.cc:290-292), but mb is assigned at :255, behind the call of
+ *     ComputeStereoMatches at :230, and the constructor's initialiser list (:192-195) does not set it: the value read is
+ *     indeterminate.  So it is an input here.
+ *   Pruning  (:340-353) median = the int distance of rank size / 2 among the accepted points' sorted distances - the UPPER
+ *            median; thDist = 1.5f * 1.4f * (float)median, left to right; every accepted point with (float)dist >= thDist
+ *            loses its observation: u_right = depth = -1, MOVBA_STEREO_REJ_FAR.  (Walking the sorted pairs from the back until
+ *            the first below thDist is exactly that: no order is observable, only the median's value.)  A median of 0 gives
+ *            thDist 0 and prunes EVERY accepted point - kept as it is.  Without an accepted point the reference indexes an
+ *            empty vector; here nothing is pruned, median_dist = -1 and th_dist = 0.
+ *   Point    (:836-851) for z = depth[i] > 0: x = (u - cx) * z * invfx, y = (v - cy) * z * invfy, left to right in fp32 with
+ *            invfx = 1.0f / fx, (u, v) = pt_un[i] - mvKeysUn, which is mvKeys whenever mDistCoef[0] == 0 (:684-688); sel_cam =
+ *            (x, y, z).  sel_point = Rwc * (double)sel_cam + Ow in fp64: each row's three products summed left to right, then +
+ *            Ow, without FMA.  Rwc and Ow come from the pose through the function behind movba_view_points' views and
+ *            movba_point_normals' centres, but evaluated once per frame on the HOST, without FMA, so that the device and the
+ *            header's host walk give the same sel_point bit for bit.  Those two calls evaluate the same statements on the
+ *            device, where a product may be fused with the add of its statement: a frame's centre here can differ from theirs
+ *            in the last bit.
+ *   Select   MOVBA_STEREO_SELECT_ALL (Tracking.cc:532-547): every i with depth > 0, in index order; sel_new = 1 unless
+ *            has_point says otherwise.  MOVBA_STEREO_SELECT_CLOSE (:1022-1098, :828-887): the pairs (z, i) with z > 0 sorted
+ *            ascending by z, then i; entry j = 0, 1, ... is listed, new iff has_point[i] == 0; nPoints counts either way, so
+ *            nPoints == j + 1; behind entry j the walk stops if z_j > th_depth && nPoints > max_point.  With c candidates at z
+ *            <= th_depth that lists min(n_cand, max(c, max_point) + 1) entries: max_point + 1 where few are close, not the
+ *            max_point the source's comment promises.
+ * What stays with the caller: cv::undistortPoints for non-zero distortion (pass pt_un); the N > 500 test of
+ * StereoInitialization; MapPoint and KeyFrame construction, track ids, UpdateNormalAndDepth (movba_point_normals);
+ * AssignFeaturesToGrid; the fisheye branches (Nleft != -1), which never run in this fork.
+ * A frame's result depends on that frame's data alone - the same frame alone or in any batch gives the same bits - and two calls
+ * give the same bits.
+ * Returns MOVBA_ERR_ARG for a NULL handle, descriptor or result; n_frames negative or above MOVBA_MAX_EXPRESS_IMAGES; pt_ptr NULL
+ * or not ascending from 0; more than MOVBA_MAX_STEREO_POINTS points in a frame; n_pt above MOVBA_MAX_EXPRESS_ITEMS; a NULL array
+ * that the counts make necessary (rows, cols, bf, max_disparity, th_depth, cam, select always; pt, next_pt, pt_status when n_pt
+ * > 0), or a NULL result array; rows or cols < 1; a select outside 0 .. 2; max_point < 0; bf, max_disparity, th_depth, cam,
+ * max_row_diff or min_disparity that is not finite, or fx, fy or bf <= 0; a pt or pt_un that is not finite or above 2^20 in
+ * magnitude; a next_pt of a point with pt_status != 0 that is not finite or above 2^20 in magnitude (so that the truncation to
+ * int is defined); a pose entry that is not finite, or a zero quaternion.  MOVBA_ERR_HIP as elsewhere.  Every argument is checked
+ * before anything is queued, and on a non-zero status nothing is written except `status`.  n_frames == 0: MOVBA_OK and nothing
+ * else written.
+ * One packed copy to the device, two launches - k_st_frame (a workgroup per frame: the gates, the exact upper median by a radix
+ * select over the int distances, the pruning, and the selection - a compaction in index order or a bitonic sort of 8-byte keys,
+ * the depth's bits above the index, in LDS) and k_st_emit (sel_ptr from the frames' counts, the selected points' rows, the
+ * padding) - and one synchronisation; result arrays that lie in movba_host_alloc memory are written by the kernels themselves.
+ * May share a handle with an uploaded or solved window, waiting for the window's arrays before it reuses the staging buffer:
+ * the window, its results, its marginals and later runs stay as they were. */
+int  movba_stereo_points(movba_handle *h, const movba_stereo_desc *desc, movba_stereo_result *res);
 
 #ifdef __cplusplus
 }

@@ -139,7 +139,7 @@ MOVBA_INTERNAL int ensure_arena(movba_handle *h, size_t bytes);
 MOVBA_INTERNAL int ensure_stage(movba_handle *h, size_t bytes);
 // The front of every call that borrows the staging buffer and the pose scratch beside the LBA calls (movba_pose_opt,
 // movba_pose_opt_batch, movba_triangulate, the front of movba_two_view / movba_two_view_lo, movba_init_map, movba_view_points,
-// movba_point_normals, movba_lba_point_normals, movba_covisibility, movba_track_match, movba_express, movba_advance, movba_mv_raster, movba_lk_track): the device is set, the pose scratch holds dev_bytes (0: the call needs no
+// movba_point_normals, movba_lba_point_normals, movba_covisibility, movba_track_match, movba_express, movba_advance, movba_mv_raster, movba_lk_track, movba_stereo_points): the device is set, the pose scratch holds dev_bytes (0: the call needs no
 // device copy yet) and the staging buffer stage_bytes, and nothing of an earlier call or upload is still using either.
 MOVBA_INTERNAL int begin_side_call(movba_handle *h, size_t dev_bytes, size_t stage_bytes);
 // device view of [p, p + bytes) if it lies inside a movba_host_alloc block, else nullptr

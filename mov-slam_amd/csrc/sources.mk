@@ -8,10 +8,11 @@
 # tests/express/Makefile (MOVBA_HOST_SRCS plus MOVBA_HOST_SRCS_EXPRESS and its own fake launch) and by
 # tests/advance/Makefile (MOVBA_HOST_SRCS plus MOVBA_HOST_SRCS_ADVANCE and its own fake launch) and by
 # tests/mv_raster/Makefile (MOVBA_HOST_SRCS plus MOVBA_HOST_SRCS_MVRASTER and its own fake launch) and by
-# tests/lk/Makefile (MOVBA_HOST_SRCS plus MOVBA_HOST_SRCS_LK and its own fake launch).
+# tests/lk/Makefile (MOVBA_HOST_SRCS plus MOVBA_HOST_SRCS_LK and its own fake launch) and by
+# tests/stereo_points/Makefile (MOVBA_HOST_SRCS plus MOVBA_HOST_SRCS_STEREO and its own fake launch).
 MOVBA_HIP_SRCS  := kernels.hip pcg_kernel.hip band_kernel.hip dense_solve.hip dense_persist.hip struct_kernels.hip struct_sort.hip \
                    pose_kernels.hip marginals.hip triangulate.hip two_view.hip init_map.hip view_points.hip point_normals.hip \
-                   covisibility.hip track_match.hip express.hip advance.hip mv_raster.hip lk.hip
+                   covisibility.hip track_match.hip express.hip advance.hip mv_raster.hip lk.hip stereo_points.hip
 MOVBA_HOST_SRCS := api.cpp upload.cpp structure.cpp dense_plan.cpp pcg_plan.cpp pose_opt.cpp marginals.cpp triangulate.cpp two_view.cpp
 # host sources whose launch the shared fake device does not stand in for: part of both libraries (csrc/Makefile), not of the
 # host-side builds that link MOVBA_HOST_SRCS against tests/hipstub's fixed set of fake launches (tests/init_map has its own)
@@ -33,5 +34,7 @@ MOVBA_HOST_SRCS_ADVANCE := advance.cpp
 MOVBA_HOST_SRCS_MVRASTER := mv_raster.cpp
 # and for movba_lk_track (tests/lk has its fake launch)
 MOVBA_HOST_SRCS_LK := lk.cpp
+# and for movba_stereo_points (tests/stereo_points has its fake launch)
+MOVBA_HOST_SRCS_STEREO := stereo_points.cpp
 # host sources with a kernel file of the same stem: the kernels' object is <stem>_kernels.o
-MOVBA_SAME_STEM := marginals triangulate two_view init_map view_points point_normals covisibility track_match express advance mv_raster lk
+MOVBA_SAME_STEM := marginals triangulate two_view init_map view_points point_normals covisibility track_match express advance mv_raster lk stereo_points

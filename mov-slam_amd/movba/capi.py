@@ -229,6 +229,27 @@ class LkResult(C.Structure):
                 ("status", C.c_int32), ("pad", C.c_int32)]
 
 
+class StereoDesc(C.Structure):
+    _fields_ = [("n_frames", C.c_int32), ("pad", C.c_int32), ("pt_ptr", _i), ("pt", _f), ("next_pt", _f), ("pt_status", _u), ("pt_un", _f),
+                ("rows", _i), ("cols", _i), ("bf", _f), ("max_disparity", _f), ("th_depth", _f), ("cam", _f), ("select", _i), ("poses", _d),
+                ("has_point", _u), ("max_row_diff", C.c_float), ("min_disparity", C.c_float), ("max_point", C.c_int32), ("pad2", C.c_int32)]
+
+
+class StereoResult(C.Structure):
+    _fields_ = [("u_right", _f), ("depth", _f), ("code", _u), ("n_stereo", _i), ("median_dist", _i), ("th_dist", _f), ("sel_ptr", _i),
+                ("sel_src", _i), ("sel_new", _u), ("sel_cam", _f), ("sel_point", _d), ("status", C.c_int32), ("pad", C.c_int32)]
+
+
+# (key, dtype, width, which count it is sized by) of movba_stereo_result
+STEREO_ARRAYS = (("u_right", np.float32, 1, "pt"), ("depth", np.float32, 1, "pt"), ("code", np.uint8, 1, "pt"),
+                 ("n_stereo", np.int32, 1, "frames"), ("median_dist", np.int32, 1, "frames"), ("th_dist", np.float32, 1, "frames"),
+                 ("sel_ptr", np.int32, 1, "ptr"), ("sel_src", np.int32, 1, "pt"), ("sel_new", np.uint8, 1, "pt"),
+                 ("sel_cam", np.float32, 3, "pt"), ("sel_point", np.float64, 3, "pt"))
+# movba_stereo_desc::select, movba_stereo_result::code (MOVBA_STEREO_*) and the bound of a frame
+STEREO_SELECT_NONE, STEREO_SELECT_ALL, STEREO_SELECT_CLOSE = 0, 1, 2
+STEREO_OK = 1
+STEREO_REJ_STATUS, STEREO_REJ_ROW, STEREO_REJ_DISPARITY, STEREO_REJ_FAR = range(16, 20)
+MAX_STEREO_POINTS = 16384
 # (key, dtype, width, which count it is sized by) of movba_lk_result
 LK_ARRAYS = (("next_pt", np.float32, 2, "pt"), ("pt_status", np.uint8, 1, "pt"), ("err", np.float32, 1, "pt"),
              ("exit_code", np.uint8, 1, "pt"), ("keep", np.uint8, 1, "pt"), ("kept_ptr", np.int32, 1, "ptr"), ("kept_src", np.int32, 1, "pt"))
@@ -310,7 +331,7 @@ EXPORTS = ["movba_version", "movba_status_string", "movba_create", "movba_destro
            "movba_host_alloc", "movba_host_free", "movba_dense_plan_probe", "movba_pose_opt_batch", "movba_lba_marginals", "movba_triangulate",
            "movba_two_view", "movba_two_view_samples", "movba_two_view_lo", "movba_init_map", "movba_view_points",
            "movba_point_normals", "movba_lba_point_normals", "movba_covisibility", "movba_track_match", "movba_express",
-           "movba_express_grid", "movba_advance", "movba_mv_raster", "movba_lk_track"]
+           "movba_express_grid", "movba_advance", "movba_mv_raster", "movba_lk_track", "movba_stereo_points"]
 
 _libs = {False: None, True: None}
 
@@ -381,6 +402,7 @@ def lib(hooks: bool = False):
         L.movba_advance.argtypes = [C.c_void_p, C.POINTER(AdvanceDesc), C.POINTER(AdvanceResult)]
         L.movba_mv_raster.argtypes = [C.c_void_p, C.POINTER(MvRasterDesc), C.POINTER(MvRasterResult)]
         L.movba_lk_track.argtypes = [C.c_void_p, C.POINTER(LkDesc), C.POINTER(LkResult)]
+        L.movba_stereo_points.argtypes = [C.c_void_p, C.POINTER(StereoDesc), C.POINTER(StereoResult)]
         L.movba_host_alloc.argtypes = [C.c_size_t]
         L.movba_host_alloc.restype = C.c_void_p
         L.movba_dense_plan_probe.argtypes = [C.c_int32, C.c_int32, C.c_int32, _i, _i, C.c_int32, _i, C.c_int32]
@@ -984,6 +1006,63 @@ def lk_result(n_frames, n_pt, alloc=np.zeros):
     return r, keep
 
 
+def stereo_desc(frames, max_row_diff=4.0, min_disparity=0.0, max_point=100):
+    """frames: one dict per stereo frame with pt (n, 2), next_pt (n, 2) and pt_status (n,) - Solver.lk_track's input and output
+    arrays as they are -, rows and cols (the right image's), bf, max_disparity, th_depth, cam (fx fy cx cy), select
+    (STEREO_SELECT_*, default NONE) and optionally pt_un (n, 2), pose (7: Tcw) and has_point (n,).  An optional array that one frame
+    has is filled in for the others with what its absence means (pt, the identity, zeros); one that no frame has is passed as
+    NULL -> (movba_stereo_desc, the arrays it points into)."""
+    nf = len(frames)
+    parts = [np.asarray(fr["pt"], np.float32).reshape(-1, 2) for fr in frames]
+    n = [len(a) for a in parts]
+
+    def cat(key, dtype, width, default):
+        for k, fr in enumerate(frames):
+            if default is None and fr.get(key) is None:
+                raise ValueError(f"stereo_desc: frame {k} has no {key}")
+        rows = [np.asarray(fr[key], dtype).reshape((-1, width) if width > 1 else (-1,)) if fr.get(key) is not None else default(k)
+                for k, fr in enumerate(frames)]
+        for k, a in enumerate(rows):
+            if len(a) != n[k]:
+                raise ValueError(f"stereo_desc: {key} of frame {k} has {len(a)} rows for {n[k]} points")
+        return np.ascontiguousarray(np.concatenate(rows) if rows else np.zeros((0, width) if width > 1 else (0,)), dtype)
+
+    keep = dict(pt_ptr=np.concatenate([[0], np.cumsum(n)]).astype(np.int32),
+                pt=np.ascontiguousarray(np.concatenate(parts) if parts else np.zeros((0, 2)), np.float32),
+                next_pt=cat("next_pt", np.float32, 2, None), pt_status=cat("pt_status", np.uint8, 1, None))
+    keep["pt_un"] = cat("pt_un", np.float32, 2, lambda k: parts[k]) if any(fr.get("pt_un") is not None for fr in frames) else None
+    keep["has_point"] = (cat("has_point", np.uint8, 1, lambda k: np.zeros(n[k], np.uint8))
+                         if any(fr.get("has_point") is not None for fr in frames) else None)
+    identity = np.array([0, 0, 0, 1, 0, 0, 0], np.float64)
+    keep["poses"] = (np.ascontiguousarray([np.asarray(fr["pose"], np.float64).reshape(7) if fr.get("pose") is not None else identity
+                                           for fr in frames], np.float64).reshape(nf, 7)
+                     if any(fr.get("pose") is not None for fr in frames) else None)
+    for key, dtype in (("rows", np.int32), ("cols", np.int32), ("bf", np.float32), ("max_disparity", np.float32), ("th_depth", np.float32)):
+        keep[key] = np.array([fr[key] for fr in frames], dtype).reshape(nf)
+    keep["select"] = np.array([fr.get("select", STEREO_SELECT_NONE) for fr in frames], np.int32).reshape(nf)
+    keep["cam"] = np.ascontiguousarray([np.asarray(fr["cam"], np.float32).reshape(4) for fr in frames], np.float32).reshape(nf, 4)
+    d = StereoDesc()
+    d.n_frames = nf
+    types = {np.dtype(np.int32): _i, np.dtype(np.float32): _f, np.dtype(np.uint8): _u, np.dtype(np.float64): _d}
+    for key in ("pt_ptr", "pt", "next_pt", "pt_status", "pt_un", "rows", "cols", "bf", "max_disparity", "th_depth", "cam", "select", "poses",
+                "has_point"):
+        if keep[key] is not None:
+            setattr(d, key, _p(keep[key], types[keep[key].dtype]))
+    d.max_row_diff, d.min_disparity, d.max_point = max_row_diff, min_disparity, max_point
+    return d, keep
+
+
+def stereo_result(n_frames, n_pt, alloc=np.zeros):
+    """-> (movba_stereo_result with its output arrays, the arrays it points into)"""
+    size = dict(pt=n_pt, ptr=n_frames + 1, frames=n_frames)
+    types = {np.int32: _i, np.uint8: _u, np.float32: _f, np.float64: _d}
+    keep, r = {}, StereoResult()
+    for key, dtype, width, which in STEREO_ARRAYS:
+        keep[key] = alloc((size[which], width) if width > 1 else (size[which],), dtype)
+        setattr(r, key, _p(keep[key], types[dtype]))
+    return r, keep
+
+
 def run_batch(solvers) -> int:
     """movba_lba_run_batch over the resident windows of `solvers` (created on one stream); download each as usual."""
     arr = (C.c_void_p * len(solvers))(*[s._h for s in solvers])
@@ -1457,6 +1536,21 @@ class Solver:
         rc = self._L.movba_lk_track(self._h, C.byref(d), C.byref(r))
         if rc < 0:
             raise MovbaError(f"movba_lk_track: {status_string(rc)}")
+        out.update(status=rc, pt_ptr=keep["pt_ptr"])
+        return out
+
+    def stereo_points(self, frames, max_row_diff=4.0, min_disparity=0.0, max_point=100, pinned=False) -> dict:
+        """movba_stereo_points (the stereo gates behind the left-to-right LK call, the median-distance pruning, the un-projection
+        and the choice of new map points, for the keypoints of many frames): frames as stereo_desc - they take lk_track's pt,
+        next_pt and pt_status as they are -> dict(status, u_right, depth, code (n_pt,), n_stereo, median_dist, th_dist
+        (n_frames,), sel_ptr (n_frames + 1,), sel_src, sel_new (n_pt, padded with -1 / 0 behind sel_ptr[-1]), sel_cam, sel_point
+        (n_pt, 3, padded with NaN), pt_ptr).  u_right and depth are what lba obs_right and triangulate's ur1 / depth1 take.  The
+        defaults are the reference's.  pinned: result arrays in movba_host_alloc memory, written by the kernels themselves."""
+        d, keep = stereo_desc(frames, max_row_diff, min_disparity, max_point)
+        r, out = stereo_result(d.n_frames, len(keep["pt"]), self._pinned if pinned else np.zeros)
+        rc = self._L.movba_stereo_points(self._h, C.byref(d), C.byref(r))
+        if rc < 0:
+            raise MovbaError(f"movba_stereo_points: {status_string(rc)}")
         out.update(status=rc, pt_ptr=keep["pt_ptr"])
         return out
 
